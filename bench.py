@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- training-step throughput of the neunet dense hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload headline|c1|c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload headline|c1|c2|c3|c4|c5] [--full] [--dump-outputs DIR]
 
 BASELINE.json's metric: "samples/sec training step (MNIST-MLP & GPT-tiny) at 1/2/4/8 GPUs; Linear fwd GFLOP/s vs
-MFMA peak".  The default workload ("headline") therefore measures, in ONE process per GPU and ONE JSON line:
+MFMA peak".  A plain run of the default workload ("headline") sets up, warms up, times the steps and prints ONE JSON line:
   * value / ms_per_step : the C4 GPT-tiny training step (d512 L6 H8 d_ff2048 vocab15000, batch 64 x seq 256 per GPU,
                           weak scaling): the W warm-up + exactly K timed steps of the contract;
+  * roofline            : the GEMM-equivalent TFLOP/s of those timed steps (their HIP-event device time) vs the fp32 MFMA peak;
+  * gemm_mode           : 0 (exact fp32 MFMA) -- the run exits 4 otherwise: `dtype: f32` and `value` are defined for that mode only.
+`--dump-outputs DIR` (headline / c4) then writes what the last timed step computed: loss.npy, param.<key>.npy and grad.<key>.npy
+for every trained parameter (keys of Module.state_dict(); tensors above 32768 elements as a fixed, seeded sample of their flat
+indices), float32, under 64 MB; the inputs and the initial weights are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else it measures, each in runs of its own after the timed steps:
   * roofline            : the C2 Linear(4096->4096) forward GEMM, batch 4096 -- the metric's "Linear fwd vs MFMA peak"
                           half: HIP-event timed launches of the same gemm_f32_kernel that does 86 % of the C4 step;
   * also.c1             : MNIST-MLP (784->128->10, batch 32 per GPU) training-step samples/s, sustained over 512 steps (16 per captured graph), also with the per-replay input copy and with the separate optimizer launch;
@@ -15,12 +22,11 @@ MFMA peak".  The default workload ("headline") therefore measures, in ONE proces
   * also.c3 / also.c5   : every op of the fused micro-bench (rows 8192 x d 4096) with its HBM / MFMA fraction; the conv classifier step;
   * also.c4_strong      : (N > 1) the strong-scaling step next to the weak-scaling `value`;
   * cpu_baseline        : the NumPy oracle's FULL GPT-tiny step (forward, backward, Adam): live n = 1 on the whole per-GPU batch + the
-                          committed n = 3 collection of the same step (profiles/cpu_c4_full_batch.json);
-  * gemm_mode           : 0 (exact fp32 MFMA) -- the run exits 4 otherwise: `dtype: f32` and `value` are defined for that mode only;
+                          committed n = 3 collection of the same step (profiles/cpu_c4_full_batch.json); --workload cN: that config's;
   * also.c4_families    : every GEMM / attention launch of the step at its own shape, isolated (HIP events) and INSIDE the replayed step
                           (`instep_ms`, from the committed rocprofv3 trace, profiles/c4_instep_families.json); roofline.instep likewise;
-  * allreduce_ms, rccl  : (N > 1 or --force-dp) the gradient exchange alone (`total`) and what it adds to the step (`exposed`), RCCL's own
-                          algorithm / protocol lines;
+  * allreduce_ms        : (N > 1 or --force-dp, headline / c4) the gradient exchange alone (`total`) and what it adds to the step
+                          (`exposed`); RCCL's own algorithm / protocol lines (`rccl`) are in every N > 1 line;
   * also.linear_swish_sweep : the reference's Linear->Swish bench sweep (scripts/benchmark_linear_swish_cuda.py:127-138), its methodology.
 `--workload c1..c5` runs one BASELINE config on its own with the per-config detail (C3: per-op HBM fractions).
 
@@ -85,6 +91,13 @@ def parse():
                     help="time --cpu-full-steps full-batch (64 x 256) NumPy-oracle GPT-tiny steps, print them as JSON and exit (no GPU work): "
                          "the n >= 3 collection committed as profiles/cpu_c4_full_batch.json, which the live n = 1 sample of every line cites")
     ap.add_argument("--cpu-full-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the timed steps of the chosen workload: the headline's roofline and `also` "
+                         "legs (other configs, kernel families, the opt-in bf16x3 mode, the Linear->Swish sweep), the gradient "
+                         "exchange on its own (allreduce_ms) and the CPU baseline.  Off: setup, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, updated parameters, gradients; "
+                         "a fixed sample of the larger tensors) as DIR/<name>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -208,6 +221,64 @@ def traffic_source():
         return f"profiles/pmc_traffic.json (rocprofv3 --pmc passes, collection {tag}; not measured by this run)"
     except Exception:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 32768             # elements kept of a larger tensor: a fixed, seeded choice of flat indices
+
+
+def named_parameters(module, prefix=""):
+    """(key, Parameter) pairs of a module tree under the keys Module.state_dict() gives them (nn/modules.py), in that order."""
+    children = getattr(module, "modules", None)
+    if isinstance(children, list):                  # Sequential / ModuleList: children keyed by their index
+        for i, m in enumerate(children):
+            if hasattr(m, "state_dict"):
+                yield from named_parameters(m, f"{prefix}{i}.")
+        return
+    for name, item in module.__dict__.items():
+        if item.__class__.__name__ == "Parameter":
+            yield prefix + name, item
+        elif hasattr(item, "state_dict"):
+            yield from named_parameters(item, prefix + name + ".")
+
+
+def dump_sample(name, a):
+    """The whole tensor (flattened) up to DUMP_SAMPLE elements, else the same DUMP_SAMPLE flat indices in every run (seeded by name)."""
+    import zlib
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if a.size <= DUMP_SAMPLE:
+        return a
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, DUMP_SAMPLE, replace=False))
+    return a[idx]
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write [(name, array)] as out_dir/<name>.npy (float32), refusing to go past DUMP_LIMIT_BYTES."""
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}", file=sys.stderr)
+
+
+def c4_step_outputs(model, loss, active):
+    """What a caller of the C4 training step holds after it: the loss, and every trained parameter with its gradient
+    (p.grad is the gradient bucket's view of the last step), each sampled by dump_sample."""
+    import torch
+    arrays = [("loss", np.asarray(loss.numpy(), dtype=np.float32).reshape(-1))]
+    seen, trained = set(), {id(p) for p in active}
+    for key, p in named_parameters(model):
+        if id(p) in seen or id(p) not in trained:
+            continue
+        seen.add(id(p))
+        arrays.append(("param." + key, dump_sample("param." + key, p.numpy())))
+        g = p.grad.detach().cpu().numpy() if isinstance(p.grad, torch.Tensor) else p.grad.numpy()
+        arrays.append(("grad." + key, dump_sample("grad." + key, g)))
+    if len(seen) != len(trained):
+        raise RuntimeError(f"--dump-outputs: {len(trained) - len(seen)} trained parameter(s) have no state_dict key")
+    return arrays
 
 
 # ------------------------------------------------------------------------------------------------ C2
@@ -760,7 +831,7 @@ def workload_c4(args, rank, world):
                 if timed:
                     a, b = ev.span()
                     a.record()
-                gstep()
+                state["loss"] = gstep()
                 if timed:
                     b.record()
         else:
@@ -769,7 +840,7 @@ def workload_c4(args, rank, world):
                     a, b = ev.span()
                     a.record()
                 opt.zero_grad()
-                fwd_bwd()
+                state["loss"] = fwd_bwd()
                 bucket.all_reduce()
                 opt.step()
                 if timed:
@@ -810,12 +881,14 @@ def workload_c4(args, rank, world):
 
     dt = timed_region(step, args.steps, args.warmup, world)
     dev_ms = ev.median_ms()
-    # ---- the gradient exchange on its own (SURVEY 8e "report all-reduce time separately"; round-5 review item 4) ----------------
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, c4_step_outputs(model, state["loss"], active))
+    # ---- the gradient exchange on its own (SURVEY 8e "report all-reduce time separately"; round-5 review item 4), --full only ------
     #   total   = every all-reduce of one step issued ALONE, event-bracketed on the stream it runs on, summed (median of 5 each)
     #   exposed = (the timed step) - (the same step, same launch mode, with the collectives muted): what the exchange adds to the
     #             step after overlap; None when the collectives are captured inside the step graph (they cannot be muted there)
     allreduce = None
-    if dp:
+    if dp and getattr(args, "full", False):
         try:
             pieces_ms = bucket.time_exchange_alone(5)
             exposed, dt_muted = None, None
@@ -1422,9 +1495,13 @@ def c4_weighted_roofline(fams):
 
 def workload_headline(args, rank, world):
     """BASELINE.json's metric in one run: C4 GPT-tiny step (value), C2 Linear forward vs MFMA peak (roofline), C1
-    MNIST-MLP samples/s and the C2 step (also)."""
+    MNIST-MLP samples/s and the C2 step (also).  Without --full: the C4 step alone, with the roofline of its own timed steps."""
     import copy
     res = workload_c4(args, rank, world)
+    if not args.full:
+        return res
+    args = copy.copy(args)
+    args.dump_outputs = None                          # the legs below run other steps: the dump is the headline step's
     c4_roof = res.pop("roofline")
     fwd = c2_forward_roofline()
     c2_obj = {
@@ -1762,6 +1839,10 @@ def main():
         r["collected"] = time.strftime("%Y-%m-%d") + " (round 6)"
         print(json.dumps(r), flush=True)
         return
+    if args.dump_outputs and args.workload not in ("headline", "c4"):
+        print(f"bench.py: --dump-outputs writes the C4 step's outputs (--workload headline or c4), not --workload {args.workload}",
+              file=sys.stderr)
+        sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_torchrun(args))
     json_out = claim_stdout()
@@ -1841,7 +1922,7 @@ def main():
     except Exception:  # noqa: BLE001
         pass
     if rank == 0:
-        if not args.no_cpu_baseline:        # N > 1 too: timed on rank 0's host cores while the other ranks wait at the barrier
+        if args.full and not args.no_cpu_baseline:  # N > 1 too: timed on rank 0's host cores while the other ranks wait at the barrier
             out["cpu_baseline"] = {"headline": cpu_headline, "c1": cpu_c1, "c2": cpu_c2, "c3": cpu_c3, "c4": cpu_c4,
                                    "c5": cpu_c5, "nb": cpu_nb}[args.workload](args.cpu_seconds)
         print(json.dumps(out), file=json_out, flush=True)

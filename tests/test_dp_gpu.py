@@ -475,7 +475,7 @@ def test_bench_eight_ranks_on_one_gpu_rehearsal():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "2", "--c4-batch", "12",
-                        "--scaling", "strong", "--dp-ingraph", "1", "--c1-steps", "32", "--no-cpu-baseline"],
+                        "--scaling", "strong", "--dp-ingraph", "1", "--c1-steps", "32", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -506,3 +506,44 @@ def test_bench_eight_ranks_on_one_gpu_rehearsal():
     assert ar["ms_per_step_collectives_muted"] > 0
     assert "rccl" in d and ("choices" in d["rccl"] or "note" in d["rccl"])
     assert d["gemm_mode"] == 0 and d["dtype"] == "f32"
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` at toy sizes: the plain line carries the headline fields and
+    nothing that --full adds, exactly K steps are timed, and the dump (loss, every trained parameter and its gradient, float32,
+    under 64 MB) is the same in two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no HIP device is visible")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, NNHIP_BENCH_TOY="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        out = str(tmp_path / f"run{i}")
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", out], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:500]
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+        assert "also" not in d and "cpu_baseline" not in d and d["allreduce_ms"] is None
+        names = sorted(f[:-4] for f in os.listdir(out))
+        arrays = {n: np.load(os.path.join(out, n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        params = [n[len("param."):] for n in names if n.startswith("param.")]
+        assert params and sorted("grad." + k for k in params) == [n for n in names if n.startswith("grad.")]
+        assert "loss" in arrays and arrays["loss"].shape == (1,) and np.isfinite(arrays["loss"]).all()
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)

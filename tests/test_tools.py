@@ -115,3 +115,56 @@ def test_bench_rccl_choices_and_device_time_guard(tmp_path):
     assert abs(bench.device_step_ms(ev, 1, 0.0215) - 0.0205) < 1e-9
     assert bench.device_step_ms(ev, 1, 0.018) is None        # above the wall time per step by more than 5 %: dropped, not reported
     assert bench.device_step_ms(bench.EventTimer(), 1, 1.0) is None
+
+
+def test_bench_dump_outputs_names_samples_and_limit(tmp_path):
+    """bench.py --dump-outputs: parameters are named by their Module.state_dict() keys, a large tensor is cut to the same seeded
+    sample in every run, everything is written as float32, and more than the limit is refused before anything is written."""
+    import sys
+
+    import numpy as np
+    import pytest
+    for p in (ROOT, os.path.join(ROOT, "numpy-nn-model_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import neunet_hip.nn as nn
+    from neunet_hip.autograd import Tensor
+    from neunet_hip.nn.modules import Module
+    from neunet_hip.nn.parameter import Parameter
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Leaf(Module):
+        def __init__(self, n):
+            super().__init__()
+            self.weight = Parameter(Tensor(np.arange(2 * n, dtype=np.float32).reshape(n, 2), device="cpu"))
+            self.bias = Parameter(Tensor(np.zeros(n, np.float32), device="cpu"))
+
+    class Net(Module):
+        def __init__(self):
+            super().__init__()
+            self.emb = Leaf(3)
+            self.layers = nn.ModuleList([Leaf(4), Leaf(5)])
+            self.head = Leaf(2)
+
+    m = Net()
+    named = list(bench.named_parameters(m))
+    assert [k for k, _ in named] == list(m.state_dict())
+    assert [id(p) for _, p in named] == [id(p) for p in m.parameters()]
+
+    small = np.arange(6, dtype=np.float64).reshape(2, 3)
+    s = bench.dump_sample("param.x", small)
+    assert s.dtype == np.float32 and np.array_equal(s, small.reshape(-1))
+    big = np.random.default_rng(0).standard_normal(bench.DUMP_SAMPLE * 3 + 7).astype(np.float32)
+    a, b = bench.dump_sample("grad.w", big), bench.dump_sample("grad.w", big.copy())
+    assert a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert not np.array_equal(a, bench.dump_sample("grad.v", big))       # the sample is seeded by the name
+
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), [("loss", np.array([1.5], np.float32)), ("grad.w", a)])
+    assert sorted(os.listdir(out)) == ["grad.w.npy", "loss.npy"]
+    assert np.load(out / "grad.w.npy").dtype == np.float32 and np.array_equal(np.load(out / "grad.w.npy"), a)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "too_big"), [("x", np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32))])
+    assert not (tmp_path / "too_big").exists()

@@ -1,8 +1,9 @@
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/r04e
-( time python bench.py > gpurun_out/r04e/bench_headline.json 2> gpurun_out/r04e/bench_headline.err ) 2>&1 | grep real
+O=${1:?usage: tools/_call.sh OUTDIR}
+mkdir -p $O
+( time python bench.py --full > $O/bench_headline.json 2> $O/bench_headline.err ) 2>&1 | grep real
 python -c "
-import json; d=json.load(open('gpurun_out/r04e/bench_headline.json')); a=d['also']
+import json, sys; d=json.load(open(sys.argv[1])); a=d['also']
 print(d['value'], d['ms_per_step'], d['roofline']['frac'])
 print('c1', a['c1']['samples_per_s'], a['c1']['launch'], a['c1']['with_input_copy']['samples_per_s'], a['c1']['separate_optimizer_launch']['samples_per_s'])
-print('c5', a['c5']['ms_per_step'])"
+print('c5', a['c5']['ms_per_step'])" $O/bench_headline.json

@@ -17,20 +17,21 @@ hipcc --offload-arch=gfx950 -O3 tools/probes/stream_nm_probe.hip -o /tmp/stream_
 timeout 900 python -m pytest tests/test_hip_parity.py -q -m gpu -k "counted_waits or wave_private" > $O/attn_sb_check.log 2>&1
 # round 6: the n = 3 collection of the full-batch NumPy-oracle step that every bench line's live n = 1 sample cites
 timeout 600 python bench.py --cpu-full-batch --cpu-full-steps 3 > $O/cpu_c4_full_batch.json 2> $O/cpu_c4_full_batch.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_headline.json 2> $O/bench_headline.err
-timeout 600 python bench.py --workload c2 --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench_c2.err
-timeout 600 python bench.py --workload c3 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
-timeout 600 python bench.py --workload c1 --steps 500 --warmup 50 > $O/bench_c1.json 2> $O/bench_c1.err
-timeout 600 python bench.py --workload c4 --steps 10 --warmup 3 > $O/bench_c4.json 2> $O/bench_c4.err
-timeout 600 python bench.py --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2> $O/bench_c5.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_headline.json 2> $O/bench_headline.err
+timeout 600 python bench.py --full --workload c2 --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 600 python bench.py --full --workload c3 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 600 python bench.py --full --workload c1 --steps 500 --warmup 50 > $O/bench_c1.json 2> $O/bench_c1.err
+timeout 600 python bench.py --full --workload c4 --steps 10 --warmup 3 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 600 python bench.py --full --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2> $O/bench_c5.err
 timeout 600 python bench.py --workload nb --no-cpu-baseline > $O/bench_nb.json 2> $O/bench_nb.err
 # the data-parallel step on the production backend with ONE rank: nccl (= RCCL) group, collectives forced
-timeout 600 python bench.py --workload c4 --force-dp --no-cpu-baseline > $O/bench_c4_forced_nccl.json 2> $O/bench_c4_forced_nccl.err
-timeout 600 python bench.py --workload c4 --force-dp --dp-ingraph 1 --no-cpu-baseline > $O/bench_c4_forced_nccl_ingraph.json 2> $O/bench_c4_forced_nccl_ingraph.err
+timeout 600 python bench.py --full --workload c4 --force-dp --no-cpu-baseline > $O/bench_c4_forced_nccl.json 2> $O/bench_c4_forced_nccl.err
+timeout 600 python bench.py --full --workload c4 --force-dp --dp-ingraph 1 --no-cpu-baseline > $O/bench_c4_forced_nccl_ingraph.json 2> $O/bench_c4_forced_nccl_ingraph.err
 cd /tmp && export TMPDIR=/tmp
 for W in headline c1 c2 c3 c4 c5; do
   S=30; [ $W = c4 ] && S=8; [ $W = headline ] && S=8; [ $W = c1 ] && S=200; [ $W = c5 ] && S=100
-  timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$W -o $W -- python $R/bench.py --workload $W --steps $S --warmup 5 --no-cpu-baseline > $O/prof_$W.log 2>&1
+  F=; [ $W = headline ] && F=--full        # the headline trace covers every leg of its --full line
+  timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$W -o $W -- python $R/bench.py $F --workload $W --steps $S --warmup 5 --no-cpu-baseline > $O/prof_$W.log 2>&1
 done
 for W in c2 c3; do
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $O/pmc_fetch_$W -o f -- python $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_$W.log 2>&1
@@ -44,9 +45,9 @@ timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT
 timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_dp -o dp -- python $R/bench.py --workload c4 --force-dp --dp-op avg --steps 5 --warmup 2 --no-cpu-baseline > $O/prof_dp.log 2>&1
 # the same DP step with the exchange through the library's own RCCL entry points (nnhipAllReduce*F32, NativeComm), and the
 # lock-step GEMM default of N > 1 jobs on / off (step time; fabric bytes of the step's GEMMs in two FETCH_SIZE passes)
-timeout 600 python $R/bench.py --workload c4 --force-dp --comm native --dp-op avg --no-cpu-baseline > $O/bench_c4_native_comm.json 2> $O/bench_c4_native_comm.err
+timeout 600 python $R/bench.py --full --workload c4 --force-dp --comm native --dp-op avg --no-cpu-baseline > $O/bench_c4_native_comm.json 2> $O/bench_c4_native_comm.err
 for LS in 0 1; do
-  NNHIP_GEMM_LOCKSTEP=$LS timeout 600 python $R/bench.py --workload c4 --force-dp --dp-op avg --no-cpu-baseline > $O/bench_c4_forced_lockstep$LS.json 2> $O/bench_c4_forced_lockstep$LS.err
+  NNHIP_GEMM_LOCKSTEP=$LS timeout 600 python $R/bench.py --full --workload c4 --force-dp --dp-op avg --no-cpu-baseline > $O/bench_c4_forced_lockstep$LS.json 2> $O/bench_c4_forced_lockstep$LS.err
   NNHIP_GEMM_LOCKSTEP=$LS timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $O/pmc_fetch_c4_ls$LS -o f -- python $R/bench.py --workload c4 --force-dp --dp-op avg --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_c4_ls$LS.log 2>&1
 done
 # MFMA-bound conv layers (conv_mfma.hip): kernel stats + SQ counters of one 64->128 ch 56x56 B64 layer
