@@ -591,6 +591,44 @@ int nnhipAllReduceAvgF32(nnhipComm_t comm, float* buf, int64_t n, nnhipStream_t 
 /* buf on every rank = buf of `root` (identical initial parameters: SURVEY 8e "broadcast from rank 0 or same seed"). */
 int nnhipBroadcastF32(nnhipComm_t comm, float* buf, int64_t n, int root, nnhipStream_t stream);
 
+/* ---- nn.LSTM (net-new exports, ABI 211: the reference has no CUDA LSTM; CPU semantics neunet/nn/layers/lstm.py:312-362 forward,
+ *      :16-143 backward) ----------------------------------------------------------------------------------------------------
+ * One layer, batch-major X [B, T, in].  Gate order f, i, o, c (the reference's parameter order, lstm.py:188-247); the layout is
+ * X W (weights [in, H] / [H, H]), not X W^T:
+ *   f, i, o = rnl(X_t W_{f,i,o} + h_{t-1} W_h{f,i,o} + b),  g = nl(X_t W_c + h_{t-1} W_hc + b_c),
+ *   c_t = f c_{t-1} + i g,  h_t = o nl(c_t).
+ * Every recurrence is ONE launch whatever T is (csrc/recurrent.hip); the input projection and the parameter gradients are
+ * whole-sequence GEMMs around it.  1 <= H <= 512.  Hp below is H rounded up to a multiple of 16.
+ * Saved state (caller-allocated, written by the forward, read by the backward):
+ *   gates [B, T, 4Hp]  activated f | i | o | g per row (columns >= H of each gate block are padding),
+ *   cell  [B, T+1, H]  c_{t-1} at index t (index 0 = c0),   hprev [B, T, H]  h_{t-1}.
+ * h0 / c0 [B, H] may be NULL (zeros).  hT / cT [B, H] (NULL-able) receive the last state and may alias h0 / c0 (cycled states).
+ * The backward takes the gradient of the whole sequence dY [B, T, H] and/or of the last state alone dYlast [B, H] (either may be
+ * NULL, not both) and writes dX [B, T, in] (NULL-able) and the twelve parameter gradients (each NULL-able; written, not
+ * accumulated).  No gradient flows into h0 / c0 (the reference gives none either).  Scratch (packed weights, the pre-activation
+ * gate gradients dG [B, T, 4Hp]) comes from the library's grow-only workspace: nothing allocates or synchronises once it has
+ * grown, so both entries can be captured into a hipGraph. */
+#define NNHIP_LSTM_TANH 0
+#define NNHIP_LSTM_SIGMOID 1
+#define NNHIP_LSTM_RELU 2
+typedef struct nnhipLSTMWeights {
+    const float* wx[4];   /* weight_f, weight_i, weight_o, weight_c      [in, H] */
+    const float* wh[4];   /* weight_hf, weight_hi, weight_ho, weight_hc  [H, H]  */
+    const float* b[4];    /* bias_f, bias_i, bias_o, bias_c              [H]; NULL = zero */
+} nnhipLSTMWeights;
+typedef struct nnhipLSTMGrads {
+    float* dwx[4];
+    float* dwh[4];
+    float* db[4];
+} nnhipLSTMGrads;
+int nnhipLSTMForward(const float* X, const nnhipLSTMWeights* w, const float* h0, const float* c0, float* Y, float* gates,
+                     float* cell, float* hprev, float* hT, float* cT, int64_t B, int64_t T, int64_t in_features,
+                     int64_t hidden, int nonlinearity, int recurrent_nonlinearity, nnhipStream_t stream);
+int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, const float* gates, const float* cell, const float* hprev,
+                      const float* dY, const float* dYlast, float* dX, const nnhipLSTMGrads* grads, int64_t B, int64_t T,
+                      int64_t in_features, int64_t hidden, int nonlinearity, int recurrent_nonlinearity,
+                      nnhipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

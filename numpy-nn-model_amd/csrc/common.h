@@ -36,7 +36,8 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // Grow-only per-process device workspace (split-K slabs, column-sum partials).  Freed by
 // nnhipCleanup().  Growing it synchronises the device (hipFree) -- it happens at most a few times.
 void* workspace(size_t bytes);
-void* workspace_arena(int which, size_t bytes);   // 0 = the general block (== workspace), 1 = the grouped dW launch's slabs
+void* workspace_arena(int which, size_t bytes);   // 0 = the general block (== workspace), 1 = the grouped dW launch's slabs,
+                                                  // 2 = the LSTM entries' packed weights and dG (recurrent.hip), which call GEMMs on block 0
 bool workspace_locked();               // nnhipWorkspaceLock(1): a captured hipGraph holds library-owned addresses -- nothing may move
 // Deferred parameter gradients (nnhipWeightGradDefer, linear.hip): on while Tensor.backward() walks the tape.  conv2d.hip queues the
 // REDUCE of a small-channel conv's per-image partial weight gradients behind it (the partials sit in an arena of their own, not
@@ -64,7 +65,7 @@ unsigned* sync_words();
 // (today: the optimizer-in-backward arrival barrier timing out, gemm_small.hip) stores a NNHIP_DEVERR_* code there with a
 // system-scope store and carries on WITHOUT its side effect; the host reads the word with a plain load -- no synchronisation --
 // and turns it into the sticky status NNHIP_EDEVICE.  nullptr when the allocation failed (kernels then just skip the store).
-enum DeviceErrorCode { NNHIP_DEVERR_NONE = 0, NNHIP_DEVERR_MLP_BARRIER = 1 };
+enum DeviceErrorCode { NNHIP_DEVERR_NONE = 0, NNHIP_DEVERR_MLP_BARRIER = 1, NNHIP_DEVERR_LSTM_SHAPE = 2 };
 unsigned* device_error_word();                   // device-side address
 int device_error_status(const char* who);        // 0, or NNHIP_EDEVICE with the message set
 // Order this launch behind the previous user of the sync words / ticket partials when it arrives on another stream (runtime.hip).

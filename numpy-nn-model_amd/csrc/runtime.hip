@@ -27,8 +27,10 @@ static std::mutex g_ws_mu;
 // Two grow-only blocks: 0 = the general workspace (split-K slabs, column-sum partials, ...), 1 = the slabs of the GROUPED parameter-
 // gradient launch (gemm.hip: gemm_f32_wgrad_group) -- its own block because that launch may run on a side stream next to kernels of
 // the main stream that use block 0 (neunet_hip/_lib.py: NNHIP_WGRAD_STREAM; round 6).
-static void* g_ws[2] = {nullptr, nullptr};
-static size_t g_ws_bytes[2] = {0, 0};
+// 2 = the LSTM entries' scratch (packed gate weights, dG): those entries call the GEMM and column-sum kernels, which take block 0,
+// while their own scratch is live (recurrent.hip; ABI 211).
+static void* g_ws[3] = {nullptr, nullptr, nullptr};
+static size_t g_ws_bytes[3] = {0, 0, 0};
 static bool g_ws_locked = false;   // nnhipWorkspaceLock: a captured hipGraph holds the blocks' addresses
 
 void* workspace_arena(int which, size_t bytes) {
@@ -147,6 +149,8 @@ static const char* device_error_text(unsigned code) {
         case NNHIP_DEVERR_MLP_BARRIER:
             return "the optimizer-in-backward launch (nnhipLinearReLULinearBackwardAdam) waited 20 s for its blocks to check in and gave up: "
                    "the W2 / b2 update of that step was skipped, the optimizer state is half-stepped";
+        case NNHIP_DEVERR_LSTM_SHAPE:
+            return "an LSTM recurrence kernel (recurrent.hip) was launched with a shape its variant cannot hold; its outputs were not written";
         default: return "unknown device error code";
     }
 }
@@ -172,7 +176,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 210; }
+extern "C" int nnhipVersion(void) { return 211; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 
@@ -214,7 +218,7 @@ extern "C" int nnhipCleanup(void) {
     nnhip::g_ws_locked = false;
     int rc = 0;
     bool synced = false;
-    for (int w = 0; w < 2; ++w) {
+    for (int w = 0; w < 3; ++w) {
         if (!nnhip::g_ws[w]) continue;
         if (!synced) { (void)hipDeviceSynchronize(); synced = true; }
         hipError_t e = hipFree(nnhip::g_ws[w]);

@@ -39,6 +39,16 @@ class Pool2dDesc(ctypes.Structure):
     _fields_ = [(n, c_int64) for n in ("B", "C", "H", "W", "kh", "kw", "sh", "sw", "pu", "pd", "pl", "pr", "dh", "dw")]
 
 
+class LSTMWeights(ctypes.Structure):
+    """struct nnhipLSTMWeights (include/neunet_hip.h): gate order f, i, o, c."""
+    _fields_ = [("wx", c_void_p * 4), ("wh", c_void_p * 4), ("b", c_void_p * 4)]
+
+
+class LSTMGrads(ctypes.Structure):
+    """struct nnhipLSTMGrads (include/neunet_hip.h)."""
+    _fields_ = [("dwx", c_void_p * 4), ("dwh", c_void_p * 4), ("db", c_void_p * 4)]
+
+
 P = c_void_p  # device pointers travel as void*
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -129,6 +139,10 @@ _SIGNATURES = {
     "nnhipFusedOptimizerSetGradDivisor": (ctypes.c_int, [c_void_p, P]),
     "nnhipConv2dForward": (ctypes.c_int, [P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConv2dBackward": (ctypes.c_int, [P, P, P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
+    "nnhipLSTMForward": (ctypes.c_int, [P, POINTER(LSTMWeights), P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64,
+                                        ctypes.c_int, ctypes.c_int, c_void_p]),
+    "nnhipLSTMBackward": (ctypes.c_int, [P, POINTER(LSTMWeights), P, P, P, P, P, P, POINTER(LSTMGrads), c_int64, c_int64, c_int64,
+                                         c_int64, ctypes.c_int, ctypes.c_int, c_void_p]),
     "nnhipLeakyReLUForward": (ctypes.c_int, [P, P, c_float, c_int64, c_void_p]),
     "nnhipLeakyReLUBackward": (ctypes.c_int, [P, P, P, c_float, c_int64, c_void_p]),
     "nnhipSigmoidForward": (ctypes.c_int, [P, P, c_int64, c_void_p]),

@@ -477,8 +477,88 @@ def gen_vision():
     save("conv_classifier", **arrs)
 
 
+# --------------------------------------------------------------------------- LSTM
+_LSTM_NAMES = ["weight_f", "weight_i", "weight_o", "weight_c", "weight_hf", "weight_hi", "weight_ho", "weight_hc",
+               "bias_f", "bias_i", "bias_o", "bias_c"]
+
+
+def _lstm_params(layer):
+    return [getattr(layer, n) for n in _LSTM_NAMES]
+
+
+def gen_lstm():
+    """Single reference LSTM layers (neunet/nn/layers/lstm.py), CPU: inputs, initial weights (biases randomised so they matter),
+    outputs, dX and all twelve gradients.  One fixture per case, each well under 256 KB."""
+    seed_layers(112)
+    rng = np.random.default_rng(23)
+    # name, B (None = 2-D input), T, in, H, nonlinearity, recurrent nonlinearity, return_sequences, initial state, cycled calls
+    cases = [("lstm_h50_b17", 17, 12, 10, 50, "tanh", "sigmoid", "both", False, 1),
+             ("lstm_t28", 2, 28, 10, 50, "tanh", "sigmoid", "all", False, 1),
+             ("lstm_t1_b1", 1, 1, 6, 16, "tanh", "sigmoid", "last", False, 1),
+             ("lstm_2d", None, 5, 8, 16, "tanh", "sigmoid", "all", False, 1),
+             ("lstm_state", 3, 4, 8, 16, "tanh", "sigmoid", False, True, 1),
+             ("lstm_cycled", 2, 3, 8, 16, "tanh", "sigmoid", True, False, 2),
+             ("lstm_relu", 4, 6, 5, 20, "relu", "tanh", "all", False, 1),
+             ("lstm_relu_rec", 3, 5, 4, 24, "tanh", "relu", "last", False, 1)]
+    for name, B, Tn, n_in, H, nl, rnl, rs, state, calls in cases:
+        layer = nn.LSTM(n_in, H, nonlinearity=nl, recurrent_nonlinearity=rnl, return_sequences=rs, cycled_states=calls > 1)
+        params = _lstm_params(layer)
+        for b in params[8:]:
+            b.data[...] = rng.uniform(-0.3, 0.3, b.data.shape)
+        arrs = {f"p{i}": q.data.copy() for i, q in enumerate(params)}
+        arrs["cfg"] = np.array([-1 if B is None else B, Tn, n_in, H, calls])
+        arrs["modes"] = np.array([nl, rnl, str(rs)])
+        Bx = 1 if B is None else B
+        if state:
+            arrs["h0"] = rng.uniform(-1, 1, (Bx, H)).astype(F32)
+            arrs["c0"] = rng.uniform(-1, 1, (Bx, H)).astype(F32)
+        for c in range(calls):
+            X = rng.uniform(-1, 1, (Tn, n_in) if B is None else (B, Tn, n_in)).astype(F32)
+            x = T(X)
+            out = layer(x, arrs.get("h0"), arrs.get("c0")) if state else layer(x)
+            outs = out if isinstance(out, tuple) else (out,)
+            arrs[f"X{c}"] = X
+            for k, o in enumerate(outs):
+                dY = rng.uniform(-1, 1, o.data.shape).astype(F32)
+                o.backward(dY)
+                arrs[f"Y{c}_{k}"], arrs[f"dY{c}_{k}"] = o.data.copy(), dY
+            arrs[f"dX{c}"] = x.grad
+        for i, q in enumerate(params):
+            arrs[f"g{i}"] = q.grad
+        save(name, **arrs)
+
+    # (b) the recurrent classifier of examples/recurrent_digits_classifier.ipynb at H = 32, batch 4, two Adam steps
+    seed_layers(113)
+    lstm1 = nn.LSTM(28, 32, return_sequences=True)
+    lstm2 = nn.LSTM(32, 32, return_sequences=False)
+    fc1 = nn.Linear(32, 10)
+    sig, mse = nn.Sigmoid(), nn.MSELoss()
+    params = _lstm_params(lstm1) + _lstm_params(lstm2) + [fc1.weight, fc1.bias]
+    p0 = [q.data.copy() for q in params]
+    opt = Adam(params, lr=0.001)
+    Xb = rng.uniform(-1, 1, (2, 4, 28, 28)).astype(F32)
+    lab = rng.integers(0, 10, (2, 4))
+    Tb = np.zeros((2, 4, 10), F32)
+    for st in range(2):
+        Tb[st, np.arange(4), lab[st]] = 1
+    losses, outs = [], []
+    for st in range(2):
+        opt.zero_grad()
+        h = lstm2(lstm1(T(Xb[st])))
+        out = sig(fc1(h.reshape(h.shape[0], -1)))
+        loss = mse(out, T(Tb[st], requires_grad=False))
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.data))
+        outs.append(out.data.copy())
+    arrs = dict(X=Xb, T=Tb, losses=np.array(losses), outs=np.stack(outs), n_params=np.int64(len(params)))
+    for i, (a, q) in enumerate(zip(p0, params)):
+        arrs[f"p{i}"], arrs[f"pf{i}"] = a, q.data
+    save("lstm_classifier", **arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
-              gen_gpt, gen_vision, gen_maxpool_dilated]
+              gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm]
 
 
 def generate_all(out_dir=None, quiet=False):
