@@ -607,7 +607,10 @@ int nnhipBroadcastF32(nnhipComm_t comm, float* buf, int64_t n, int root, nnhipSt
  * NULL, not both) and writes dX [B, T, in] (NULL-able) and the twelve parameter gradients (each NULL-able; written, not
  * accumulated).  No gradient flows into h0 / c0 (the reference gives none either).  Scratch (packed weights, the pre-activation
  * gate gradients dG [B, T, 4Hp]) comes from the library's grow-only workspace: nothing allocates or synchronises once it has
- * grown, so both entries can be captured into a hipGraph. */
+ * grown, so both entries can be captured into a hipGraph.
+ * Refusals, all before anything is launched (no output is touched): a size < 1, hidden > 512, a nonlinearity code outside 0..2, a
+ * NULL X / weights / gate weight / Y / saved-state buffer, dY and dYlast both NULL: NNHIP_EINVAL; any pointer (members of the two
+ * structs included) that is not 4-byte aligned: NNHIP_EALIGN. */
 #define NNHIP_LSTM_TANH 0
 #define NNHIP_LSTM_SIGMOID 1
 #define NNHIP_LSTM_RELU 2

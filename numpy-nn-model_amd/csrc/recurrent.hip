@@ -424,6 +424,8 @@ extern "C" int nnhipLSTMForward(const float* X, const nnhipLSTMWeights* w, const
     const char* fn = "nnhipLSTMForward";
     if (int rc = lstm_common_checks(fn, X, w, B, T, in, H, nl, rnl)) return rc;
     NNHIP_CHECK_ARG(Y && gates && cell && hprev, NNHIP_EINVAL, "%s: null output / saved-state buffer", fn);
+    NNHIP_CHECK_ARG(aligned4(h0) && aligned4(c0) && aligned4(Y) && aligned4(gates) && aligned4(cell) && aligned4(hprev) && aligned4(hT) &&
+                        aligned4(cT), NNHIP_EALIGN, "%s: misaligned state / output buffer", fn);
     hipStream_t st = (hipStream_t)stream;
     const int Hp = (int)ceil_div(H, 16) * 16;
     const int64_t G = 4 * (int64_t)Hp;
@@ -452,6 +454,11 @@ extern "C" int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, cons
     if (int rc = lstm_common_checks(fn, X, w, B, T, in, H, nl, rnl)) return rc;
     NNHIP_CHECK_ARG(gates && cell && hprev, NNHIP_EINVAL, "%s: null saved-state buffer", fn);
     NNHIP_CHECK_ARG(dY || dYlast, NNHIP_EINVAL, "%s: null dY and dYlast", fn);
+    NNHIP_CHECK_ARG(aligned4(gates) && aligned4(cell) && aligned4(hprev) && aligned4(dY) && aligned4(dYlast) && aligned4(dX), NNHIP_EALIGN,
+                    "%s: misaligned saved-state / gradient buffer", fn);
+    for (int g = 0; grads && g < 4; ++g)
+        NNHIP_CHECK_ARG(aligned4(grads->dwx[g]) && aligned4(grads->dwh[g]) && aligned4(grads->db[g]), NNHIP_EALIGN,
+                        "%s: misaligned parameter gradient buffer", fn);
     hipStream_t st = (hipStream_t)stream;
     const int Hp = (int)ceil_div(H, 16) * 16;
     const int64_t G = 4 * (int64_t)Hp, BT = B * T;

@@ -53,6 +53,41 @@ def test_ctypes_table_matches_header(lib):
         _lib.load_hip_function(name)  # argtypes bind
 
 
+def header_struct_fields(name):
+    """[(member, array length)] of `typedef struct <name> { ... } <name>;` in the header, in declaration order; every member must be
+    a (const) float* array."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), text, flags=re.S)
+    assert m, f"struct {name} not found in include/neunet_hip.h"
+    fields = []
+    for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+        f = re.fullmatch(r"(?:const\s+)?float\s*\*\s*(\w+)\s*\[\s*(\d+)\s*\]", decl)
+        assert f, f"struct {name}: member {decl!r} is not a float* array"
+        fields.append((f.group(1), int(f.group(2))))
+    return fields
+
+
+@pytest.mark.parametrize("cname,pyname,order", [("nnhipLSTMWeights", "LSTMWeights", ["wx", "wh", "b"]),
+                                                ("nnhipLSTMGrads", "LSTMGrads", ["dwx", "dwh", "db"])])
+def test_lstm_structs_match_header(cname, pyname, order):
+    """The two structs the LSTM entries take by pointer: the ctypes mirror has the header's members, in the header's order, each an
+    array of four pointers -- twelve pointers, no padding, each member at the offset the C compiler gives it."""
+    from neunet_hip import _lib
+    cls = getattr(_lib, pyname)
+    fields = header_struct_fields(cname)
+    assert [n for n, _ in fields] == order
+    assert all(k == 4 for _, k in fields)
+    assert [n for n, _ in cls._fields_] == order
+    psz = ctypes.sizeof(ctypes.c_void_p)
+    for idx, (n, t) in enumerate(cls._fields_):
+        assert t._type_ is ctypes.c_void_p and t._length_ == 4, n
+        assert getattr(cls, n).offset == idx * 4 * psz and getattr(cls, n).size == 4 * psz, n
+    assert ctypes.sizeof(cls) == 12 * psz
+    argtypes = {"nnhipLSTMWeights": [("nnhipLSTMForward", 1), ("nnhipLSTMBackward", 1)], "nnhipLSTMGrads": [("nnhipLSTMBackward", 8)]}
+    for fn, pos in argtypes[cname]:
+        assert _lib._SIGNATURES[fn][1][pos] is ctypes.POINTER(cls), (fn, pos)
+
+
 def test_version_and_error_string(lib):
     from neunet_hip import _lib
     assert _lib.load_hip_function("nnhipVersion")() >= 100

@@ -10,8 +10,9 @@ NAMES = ["weight_f", "weight_i", "weight_o", "weight_c", "weight_hf", "weight_hi
          "bias_f", "bias_i", "bias_o", "bias_c"]
 
 
-def replay_reference(f):
-    """Run a fixture case through the float64 restatement: returns ({key: output}, dX per call, the twelve gradients)."""
+def replay_reference(f, dtype=np.float64):
+    """Run a fixture case through the restatement (float64, or the reference's own float32): returns ({key: output}, dX per call,
+    the twelve gradients)."""
     B, T, n_in, H, calls = (int(v) for v in f["cfg"])
     nl, rnl = str(f["modes"][0]), str(f["modes"][1])
     params = [f[f"p{i}"] for i in range(12)]
@@ -20,7 +21,7 @@ def replay_reference(f):
     for c in range(calls):
         X = f[f"X{c}"]
         X3 = X[None] if B < 0 else X
-        Y, cache = lstm_forward(X3, params, h0, c0, nl, rnl)
+        Y, cache = lstm_forward(X3, params, h0, c0, nl, rnl, dtype=dtype)
         keys = sorted(k for k in f if k.startswith(f"Y{c}_"))
         dX = np.zeros(X3.shape)
         for k in keys:
@@ -50,6 +51,34 @@ def test_restatement_matches_reference_fixture(golden, name):
         np.testing.assert_allclose(dX, f[f"dX{c}"], rtol=1e-4, atol=1e-6, err_msg=f"dX{c}")
     for i, g in enumerate(grads):
         np.testing.assert_allclose(g.reshape(f[f"g{i}"].shape), f[f"g{i}"], rtol=1e-4, atol=1e-5, err_msg=NAMES[i])
+
+
+def test_float32_mode_matches_reference_fixture(golden):
+    """lstm_ref's dtype=np.float32 mode is the reference's own arithmetic (float32 arrays, float32 exp / tanh): it reproduces the
+    recorded T = 28 case to the tolerances above, every array it touches is float32, and it differs from the float64 mode -- so the
+    "share of the bound the reference alone uses" figures of tests/test_lstm_tiers_gpu.py are pinned to the reference, not to our
+    reading of it."""
+    f = golden("lstm_t28")
+    outs, dXs, grads = replay_reference(f, dtype=np.float32)
+    for k, v in outs.items():
+        assert v.dtype == np.float32
+        np.testing.assert_allclose(v, f[k], rtol=1e-5, atol=1e-6, err_msg=k)
+    for c, dX in enumerate(dXs):
+        np.testing.assert_allclose(dX, f[f"dX{c}"], rtol=1e-4, atol=1e-6, err_msg=f"dX{c}")
+    for i, g in enumerate(grads):
+        np.testing.assert_allclose(g.reshape(f[f"g{i}"].shape), f[f"g{i}"], rtol=1e-4, atol=1e-5, err_msg=NAMES[i])
+    B, T, n_in, H, _ = (int(v) for v in f["cfg"])
+    params = [f[f"p{i}"] for i in range(12)]
+    Y32, cache = lstm_forward(f["X0"], params, dtype=np.float32)
+    dX32, g32 = lstm_backward(cache, dY_all=np.ones((B, T, H), np.float32))
+    for a in [Y32, dX32, *g32, *cache["hs"], *cache["cs"], *(z for zs in cache["z"] for z in zs)]:
+        assert a.dtype == np.float32
+    Y64, _ = lstm_forward(f["X0"], params)
+    assert Y64.dtype == np.float64 and np.any(Y64 != Y32) and np.abs(Y64 - Y32).max() < 1e-5
+    # a None bias is a zero bias
+    Yz, _ = lstm_forward(f["X0"], params[:8] + [None, params[9], None, None])
+    Yz2, _ = lstm_forward(f["X0"], params[:8] + [np.zeros(H), params[9], np.zeros(H), np.zeros(H)])
+    np.testing.assert_array_equal(Yz, Yz2)
 
 
 def test_lstm_parameters_match_reference(golden):
