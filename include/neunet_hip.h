@@ -632,6 +632,44 @@ int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, const float* ga
                       int64_t in_features, int64_t hidden, int nonlinearity, int recurrent_nonlinearity,
                       nnhipStream_t stream);
 
+/* ---- GPT-2 inference (net-new exports, ABI 212): LayerNorm, GELU, KV-cached decode attention ---------------------------------
+ * LayerNorm over the last axis of X [rows, cols] (neunet/nn/layers/layernorm.py:115-147): biased variance, rstd = 1/sqrt(var+eps),
+ * Y = (X - mean) rstd [* weight + bias].  weight / bias NULL: elementwise_affine=False.  Saved for the backward: mean and rstd,
+ * rows floats each (the reference keeps X_centered, a whole tensor).  The backward writes dX (closed form of layernorm.py:48-93,
+ * two row sums) and, where asked (each NULL-able), dW = sum_rows dY xhat and dB = sum_rows dY -- written, not accumulated; the Ex
+ * form adds dX_addend (an already accumulated gradient of X, e.g. the residual branch's) to dX in the same pass.  Inside
+ * nnhipWeightGradDefer(1) the finishing column sums of dW / dB ride in the RMSNorm queue and are launched by nnhipWeightGradFlush. */
+int nnhipLayerNormForward(const float* X, const float* weight, const float* bias, float* Y, float* mean, float* rstd,
+                          int64_t rows, int64_t cols, float eps, nnhipStream_t stream);
+int nnhipLayerNormBackward(const float* dY, const float* X, const float* weight, const float* mean, const float* rstd,
+                           float* dX, float* dW, float* dB, int64_t rows, int64_t cols, nnhipStream_t stream);
+int nnhipLayerNormBackwardEx(const float* dY, const float* X, const float* weight, const float* mean, const float* rstd,
+                             const float* dX_addend, float* dX, float* dW, float* dB, int64_t rows, int64_t cols,
+                             nnhipStream_t stream);
+/* GELU, tanh form (neunet/nn/activations.py:386-422): out = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))); the backward is the
+ * exact derivative of that form (the reference's uses the same constants rounded to six digits). */
+int nnhipGELUForward(float* out, const float* in, int64_t size, nnhipStream_t stream);
+int nnhipGELUBackward(float* dIn, const float* dOut, const float* in, int64_t size, nnhipStream_t stream);
+/* KV-cached attention for one new token per batch row (csrc/attention_decode.hip).
+ *   qkv       [B, 3D] (row stride ld_qkv floats, D = H * head_dim): the new token's fused projection q | k | v
+ *   Kcache, Vcache  [B, H, Tmax, head_dim] each, HEAD-MAJOR: a head's keys are one contiguous stream
+ *   cache_len DEVICE int32 [B]: tokens already cached in row b (rows may differ).  Read only: the caller advances it.
+ * Row b: k and v of the new token are written at index cache_len[b]; the query attends keys 0 .. cache_len[b] inclusive with
+ * softmax(scale q.k); O [B, D] receives the result.  Nothing depends on a host-side position, so the call can be captured into a
+ * hipGraph and replayed while cache_len advances on the device.  The key range of each (b, h) is split over blocks whose partial
+ * (max, sum, o) land in `workspace` (nnhipAttentionDecodeWorkspace bytes; it may be NULL when that returns 0) and are combined in
+ * split order: the output is bit-identical from run to run.  A row with cache_len[b] outside 0 .. Tmax-1 writes NOTHING (cache
+ * and O untouched) and raises the device error word: nnhipDeviceError() / the next call return NNHIP_EDEVICE.
+ * head_dim 32, 64 or 128, anything else: NNHIP_EINVAL.  qkv and the caches 16-byte aligned, ld_qkv % 4 == 0: else NNHIP_EALIGN. */
+int64_t nnhipAttentionDecodeWorkspace(int64_t B, int64_t H, int64_t Tmax, int64_t head_dim);   /* bytes, or a negative status */
+int nnhipAttentionDecode(const float* qkv, float* Kcache, float* Vcache, const int32_t* cache_len, float* O, float* workspace,
+                         int64_t B, int64_t H, int64_t Tmax, int64_t head_dim, int64_t ld_qkv, float scale, nnhipStream_t stream);
+/* Prefill: k and v of T tokens out of a fused projection qkv [B, T, 3D] (row stride ld_qkv) into the caches at token index
+ * cache_len[b] + i (cache_len NULL: 0 + i).  T > Tmax: NNHIP_EINVAL; a row whose cache_len leaves no room for T tokens is skipped
+ * and raises the device error word. */
+int nnhipKVCacheFill(const float* qkv, float* Kcache, float* Vcache, const int32_t* cache_len, int64_t B, int64_t H, int64_t T,
+                     int64_t Tmax, int64_t head_dim, int64_t ld_qkv, nnhipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

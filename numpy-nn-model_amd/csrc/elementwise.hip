@@ -124,6 +124,23 @@ struct SwishB {
         return dy * (beta * f + s * (1.f - beta * f));
     }
 };
+// GELU, tanh form (neunet/nn/activations.py:412-417): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3).  Since
+// 0.5 (1 + tanh u) = sigmoid(2u) the kernel evaluates x * sigmoid(2u): one exp2 and one rcp, and no 1 + tanh cancellation
+// on the negative side.
+constexpr float kGeluK = 0.7978845608028654f, kGeluC = 0.044715f;
+struct GeluF {
+    __device__ float operator()(float x) const { return x * sigmoid_fast_(2.f * kGeluK * (x + kGeluC * x * x * x)); }
+};
+// The exact derivative of that form: s + x s (1 - s) 2 du/dx, s = sigmoid(2u), du/dx = sqrt(2/pi) (1 + 3 * 0.044715 x^2).
+// (The reference's backward, activations.py:396-401, is the same expression with its constants rounded to six digits.)
+struct GeluB {
+    __device__ float operator()(float dy, float x) const {
+        const float x2 = x * x;
+        const float s = sigmoid_fast_(2.f * kGeluK * (x + kGeluC * x2 * x));
+        const float t = x * s * (1.f - s);            // exactly 0 once the sigmoid has saturated: skip the polynomial there, whose
+        return dy * (t == 0.f ? s : fmaf(t, 2.f * kGeluK * fmaf(3.f * kGeluC, x2, 1.f), s));   // x^2 overflows for |x| > 1.8e19 (0 * inf)
+    }
+};
 struct ScaleF {
     float alpha;
     __device__ float operator()(float x) const { return alpha * x; }
@@ -277,6 +294,18 @@ extern "C" int nnhipSwishBackward(float* dIn, const float* dOut, const float* in
     if (size == 0) return 0;
     NNHIP_PTRS("nnhipSwishBackward", dIn, dOut, in);
     return launch_map2(dIn, dOut, in, size, SwishB{beta}, (hipStream_t)s, "swish_backward");
+}
+extern "C" int nnhipGELUForward(float* out, const float* in, int64_t size, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipGELUForward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipGELUForward", out, in);
+    return launch_map1(out, in, size, GeluF{}, (hipStream_t)s, "gelu_forward");
+}
+extern "C" int nnhipGELUBackward(float* dIn, const float* dOut, const float* in, int64_t size, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipGELUBackward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipGELUBackward", dIn, dOut, in);
+    return launch_map2(dIn, dOut, in, size, GeluB{}, (hipStream_t)s, "gelu_backward");
 }
 extern "C" int nnhipFusedSwishAndMul(float* out, const float* in, float beta, int64_t hidden,
                                      int64_t size, nnhipStream_t s) {

@@ -695,6 +695,224 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_dwdb_cols(const float* __rest
 }
 
 // =================================================================================================
+// LayerNorm   (neunet/nn/layers/layernorm.py:115-147 fwd, 48-93 bwd; net-new kernels, ABI 212)
+// =================================================================================================
+// The row is in registers, so mean and variance are the exact two-pass ones (sum, then sum of squared deviations: no
+// E[x^2] - mean^2 cancellation).  Saved for the backward: mean and rstd = 1/sqrt(var + eps), one float each per row -- the
+// reference keeps X_centered, a whole extra tensor.  w == nullptr: elementwise_affine=False.
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void layernorm_fwd_rows(
+    const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ b,
+    float* __restrict__ Y, float* __restrict__ Mean, float* __restrict__ Rstd, int64_t rows,
+    int64_t cols, float eps, int nt) {
+    ROW_PROLOGUE(TPR)
+    RowTile<TPR, NV, VEC> r, wt;
+    r.load(X + row * cols, cols, t, 0.f, nt);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) s += r.x[e];          // (padding lanes hold 0)
+    const float invN = 1.0f / (float)cols;
+    const float mean = row_sum<TPR>(s, red) * invN;
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) {
+        r.x[e] = r.col(t, e) < cols ? r.x[e] - mean : 0.f;
+        ss += r.x[e] * r.x[e];
+    }
+    ss = row_sum<TPR>(ss, red);
+    const float rstd = 1.0f / sqrtf(ss * invN + eps);
+    if (t == 0) { Mean[row] = mean; Rstd[row] = rstd; }
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) r.x[e] *= rstd;
+    if (w) {
+        wt.load(w, cols, t, 0.f);
+#pragma unroll
+        for (int e = 0; e < r.NE; ++e) r.x[e] *= wt.x[e];
+    }
+    if (b) {
+        wt.load(b, cols, t, 0.f);
+#pragma unroll
+        for (int e = 0; e < r.NE; ++e) r.x[e] += wt.x[e];
+    }
+    r.store(Y + row * cols, cols, t);
+}
+
+// Backward, the persistent shape of rmsnorm_bwd_rows (one row per iteration with the next row's loads in flight, per-thread
+// column partials of dw = sum dy xhat and db = sum dy, one partial row per block, finished by the column-sum launch).
+// With g = w dy and xhat = (x - mean) rstd, the reference's three terms (layernorm.py:58-73) collapse to
+//   dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)):  two row sums, taken with ONE pair of barriers.
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void layernorm_bwd_rows(
+    const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
+    const float* __restrict__ Mean, const float* __restrict__ Rstd, float* __restrict__ dX,
+    float* __restrict__ part_dw, float* __restrict__ part_db, int64_t rows, int64_t cols,
+    const float* __restrict__ dXadd, int nt) {
+    constexpr int RPB = (TPR >= 256) ? 1 : 256 / TPR;
+    constexpr int NW = TPR / 64;
+    __shared__ float red[32];
+    __shared__ float4 fin_lds[RPB > 1 ? 256 : 1];
+    const int t = threadIdx.x % TPR;
+    const int rslot = RPB > 1 ? threadIdx.x / TPR : 0;
+    RowTile<TPR, NV, VEC> wt, adw, adb;
+    if (w) wt.load(w, cols, t, 0.f);
+#pragma unroll
+    for (int e = 0; e < wt.NE; ++e) {
+        adw.x[e] = adb.x[e] = 0.f;
+        if (!w) wt.x[e] = 1.f;
+    }
+    const float invN = 1.0f / (float)cols;
+    const int64_t step = (int64_t)gridDim.x * RPB;
+    constexpr bool PRE = TPR < 1024;   // (see rmsnorm_bwd_rows)
+    RowTile<TPR, NV, VEC> x0, g0, nx, ng;
+    const int64_t first = (int64_t)blockIdx.x * RPB + rslot;
+    if constexpr (PRE) {
+        if (first < rows) {
+            x0.load(X + first * cols, cols, t, 0.f, nt);
+            g0.load(dY + first * cols, cols, t, 0.f, nt);
+        }
+    }
+    for (int64_t r0 = first; r0 < rows; r0 += step) {
+        if constexpr (PRE) {
+            const int64_t n0 = r0 + step;
+            if (n0 < rows) {
+                nx.load(X + n0 * cols, cols, t, 0.f, nt);
+                ng.load(dY + n0 * cols, cols, t, 0.f, nt);
+            }
+        } else {
+            x0.load(X + r0 * cols, cols, t, 0.f, nt);
+            g0.load(dY + r0 * cols, cols, t, 0.f, nt);
+        }
+        const float mu = Mean[r0], rs = Rstd[r0];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < x0.NE; ++e) {
+            x0.x[e] = (x0.x[e] - mu) * rs;            // xhat (padding lanes: dy = 0 there, so nothing below sees them)
+            adb.x[e] += g0.x[e];
+            adw.x[e] += g0.x[e] * x0.x[e];
+            g0.x[e] *= wt.x[e];                       // dX_hat = w * dy
+            s1 += g0.x[e];
+            s2 += g0.x[e] * x0.x[e];
+        }
+        if constexpr (NW == 1) { s1 = wave_sum(s1); s2 = wave_sum(s2); }
+        else block_sum2<NW>(s1, s2, red);
+        s1 *= invN;
+        s2 *= invN;
+#pragma unroll
+        for (int e = 0; e < x0.NE; ++e) g0.x[e] = (g0.x[e] - s1 - x0.x[e] * s2) * rs;
+        if (dXadd) {   // dX = layernorm gradient + an already accumulated gradient of X (x0 is dead: reuse it).  __fadd_rn: a
+            // separately rounded add the compiler may not contract into the multiply above, so that the Ex entry returns
+            // EXACTLY (plain entry's dX) + addend, bit for bit
+            x0.load(dXadd + r0 * cols, cols, t, 0.f);
+#pragma unroll
+            for (int e = 0; e < x0.NE; ++e) g0.x[e] = __fadd_rn(g0.x[e], x0.x[e]);
+        }
+        g0.store(dX + r0 * cols, cols, t);
+        if constexpr (PRE) {
+#pragma unroll
+            for (int e = 0; e < x0.NE; ++e) { x0.x[e] = nx.x[e]; g0.x[e] = ng.x[e]; }
+        }
+    }
+    if (!part_dw && !part_db) return;      // elementwise_affine=False (uniform for the whole grid)
+    if constexpr (RPB > 1) {
+        float* xch = reinterpret_cast<float*>(fin_lds);
+        constexpr int NE = NV * 4;
+        constexpr int EPP = (1024 / (3 * 64)) < NE ? (1024 / (3 * 64)) : NE;
+        auto fold = [&](RowTile<TPR, NV, VEC>& acc) {
+#pragma unroll
+            for (int e0 = 0; e0 < NE; e0 += EPP) {
+                __syncthreads();
+                if (rslot > 0) {
+#pragma unroll
+                    for (int e = 0; e < EPP; ++e)
+                        if (e0 + e < NE) xch[((rslot - 1) * EPP + e) * 64 + t] = acc.x[e0 + e];
+                }
+                __syncthreads();
+                if (rslot == 0) {
+#pragma unroll
+                    for (int e = 0; e < EPP; ++e)
+                        if (e0 + e < NE)
+                            acc.x[e0 + e] += (xch[(0 * EPP + e) * 64 + t] + xch[(1 * EPP + e) * 64 + t]) + xch[(2 * EPP + e) * 64 + t];
+                }
+            }
+        };
+        if (part_dw) fold(adw);
+        if (part_db) fold(adb);
+        __syncthreads();
+    }
+    if (rslot == 0) {
+        if (part_dw) adw.store(part_dw + (int64_t)blockIdx.x * cols, cols, t);
+        if (part_db) adb.store(part_db + (int64_t)blockIdx.x * cols, cols, t);
+    }
+}
+
+// ---- LayerNorm for rows wider than the register tile (cols > 16384): looped, one block per row ------------------------
+__global__ __launch_bounds__(1024) void layernorm_fwd_looped(const float* __restrict__ X, const float* __restrict__ w,
+                                                             const float* __restrict__ b, float* __restrict__ Y,
+                                                             float* __restrict__ Mean, float* __restrict__ Rstd,
+                                                             int64_t cols, float eps) {
+    __shared__ float red[16];
+    const int64_t row = blockIdx.x;
+    const float* x = X + row * cols;
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < cols; i += 1024) s += x[i];
+    const float mean = block_sum<16>(s, red) / (float)cols;
+    float ss = 0.f;
+    for (int64_t i = threadIdx.x; i < cols; i += 1024) { const float d = x[i] - mean; ss += d * d; }
+    ss = block_sum<16>(ss, red);
+    const float rstd = 1.0f / sqrtf(ss / (float)cols + eps);
+    if (threadIdx.x == 0) { Mean[row] = mean; Rstd[row] = rstd; }
+    for (int64_t i = threadIdx.x; i < cols; i += 1024) {
+        float v = (x[i] - mean) * rstd;
+        if (w) v *= w[i];
+        if (b) v += b[i];
+        Y[row * cols + i] = v;
+    }
+}
+__global__ __launch_bounds__(1024) void layernorm_bwd_dx_looped(const float* __restrict__ dY, const float* __restrict__ X,
+                                                                const float* __restrict__ w, const float* __restrict__ Mean,
+                                                                const float* __restrict__ Rstd, float* __restrict__ dX,
+                                                                int64_t cols, const float* __restrict__ dXadd) {
+    __shared__ float red[32];
+    const int64_t row = blockIdx.x;
+    const float* x = X + row * cols;
+    const float* g = dY + row * cols;
+    const float mu = Mean[row], rs = Rstd[row];
+    float s1 = 0.f, s2 = 0.f;
+    for (int64_t i = threadIdx.x; i < cols; i += 1024) {
+        const float gh = w ? g[i] * w[i] : g[i];
+        s1 += gh;
+        s2 += gh * ((x[i] - mu) * rs);
+    }
+    block_sum2<16>(s1, s2, red);
+    s1 /= (float)cols;
+    s2 /= (float)cols;
+    for (int64_t i = threadIdx.x; i < cols; i += 1024) {
+        const float gh = w ? g[i] * w[i] : g[i];
+        float v = (gh - s1 - ((x[i] - mu) * rs) * s2) * rs;
+        if (dXadd) v = __fadd_rn(v, dXadd[row * cols + i]);
+        dX[row * cols + i] = v;
+    }
+}
+// dw[c] = sum_r dy[r,c] xhat[r,c], db[c] = sum_r dy[r,c]: thread per column, rows split over gridDim.y (rmsnorm_bwd_dwdb_cols)
+__global__ __launch_bounds__(256) void layernorm_bwd_dwdb_cols(const float* __restrict__ dY, const float* __restrict__ X,
+                                                               const float* __restrict__ Mean, const float* __restrict__ Rstd,
+                                                               float* __restrict__ part_dw, float* __restrict__ part_db,
+                                                               int64_t rows, int64_t cols, int64_t rows_per_block) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t r1 = min(rows, r0 + rows_per_block);
+    float aw = 0.f, ab = 0.f;
+    for (int64_t r = r0; r < r1; ++r) {
+        const float g = dY[r * cols + c];
+        aw += g * ((X[r * cols + c] - Mean[r]) * Rstd[r]);
+        ab += g;
+    }
+    if (part_dw) part_dw[(int64_t)blockIdx.y * cols + c] = aw;
+    if (part_db) part_db[(int64_t)blockIdx.y * cols + c] = ab;
+}
+
+// =================================================================================================
 // Fused CrossEntropy forward+backward
 // (CPU semantics: LogSoftmax(axis=1) -> NLLLoss, neunet/nn/losses.py:59-126; fusion boundary of
 //  cross_entropy.cu:18-229: one pass computes loss, lse and d(logits))
@@ -1710,6 +1928,107 @@ extern "C" int nnhipRMSNormBackwardEx(const float* dY, const float* X, const flo
         return 0;
     }
     return colsum_tall(part_dw, dW, part_db, db, nblk, cols, vec, st);
+}
+
+// ---- LayerNorm (ABI 212) ------------------------------------------------------------------------
+extern "C" int nnhipLayerNormForward(const float* X, const float* weight, const float* bias, float* Y, float* mean,
+                                     float* rstd, int64_t rows, int64_t cols, float eps, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(rows >= 0 && cols >= 0, NNHIP_EINVAL, "nnhipLayerNormForward: negative size");
+    if (rows == 0 || cols == 0) return 0;
+    NNHIP_CHECK_ARG(X && Y && mean && rstd, NNHIP_EINVAL, "nnhipLayerNormForward: null pointer");
+    NNHIP_CHECK_ARG(aligned4(X) && aligned4(Y) && aligned4(weight) && aligned4(bias) && aligned4(mean) && aligned4(rstd),
+                    NNHIP_EALIGN, "nnhipLayerNormForward: misaligned pointer");
+    hipStream_t st = (hipStream_t)s;
+    if (cols > kMaxRegRow) {
+        hipLaunchKernelGGL(layernorm_fwd_looped, dim3((unsigned)rows), dim3(1024), 0, st, X, weight, bias, Y, mean, rstd, cols, eps);
+    } else {
+        const bool vec = aligned16(X) && aligned16(Y) && aligned16(weight) && aligned16(bias) && cols % 4 == 0;
+        ROW_DISPATCH(layernorm_fwd_rows, cols, vec, rows, st, X, weight, bias, Y, mean, rstd, rows, cols, eps, row_streaming(rows, cols, cols));
+    }
+    NNHIP_LAUNCH_CHECK("layernorm_forward");
+    return 0;
+}
+
+extern "C" int nnhipLayerNormBackward(const float* dY, const float* X, const float* weight, const float* mean,
+                                      const float* rstd, float* dX, float* dW, float* dB, int64_t rows, int64_t cols,
+                                      nnhipStream_t s) {
+    return nnhipLayerNormBackwardEx(dY, X, weight, mean, rstd, nullptr, dX, dW, dB, rows, cols, s);
+}
+
+extern "C" int nnhipLayerNormBackwardEx(const float* dY, const float* X, const float* weight, const float* mean,
+                                        const float* rstd, const float* dX_addend, float* dX, float* dW, float* dB,
+                                        int64_t rows, int64_t cols, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(rows >= 0 && cols >= 0, NNHIP_EINVAL, "nnhipLayerNormBackward: negative size");
+    if (cols == 0) return 0;
+    NNHIP_CHECK_ARG(dY && X && mean && rstd && dX, NNHIP_EINVAL, "nnhipLayerNormBackward: null pointer");
+    NNHIP_CHECK_ARG(aligned4(dY) && aligned4(X) && aligned4(weight) && aligned4(mean) && aligned4(rstd) && aligned4(dX_addend) &&
+                    aligned4(dX) && aligned4(dW) && aligned4(dB), NNHIP_EALIGN, "nnhipLayerNormBackward: misaligned pointer");
+    hipStream_t st = (hipStream_t)s;
+    const int nparts = (dW ? 1 : 0) + (dB ? 1 : 0);
+    if (cols > kMaxRegRow) {
+        if (rows > 0) {
+            hipLaunchKernelGGL(layernorm_bwd_dx_looped, dim3((unsigned)rows), dim3(1024), 0, st, dY, X, weight, mean, rstd, dX, cols, dX_addend);
+            NNHIP_LAUNCH_CHECK("layernorm_bwd_dx_looped");
+        }
+        if (nparts == 0) return 0;
+        const int64_t col_blocks = ceil_div(cols, 256);
+        int64_t ry = 1024 / col_blocks;
+        if (ry > ceil_div(rows > 0 ? rows : 1, 8)) ry = ceil_div(rows > 0 ? rows : 1, 8);
+        if (ry < 1) ry = 1;
+        const int64_t rpb = ceil_div(rows > 0 ? rows : 1, ry);
+        ry = ceil_div(rows > 0 ? rows : 1, rpb);
+        const size_t pf = ((size_t)ry * cols + 3) / 4 * 4;
+        float* part = static_cast<float*>(workspace(pf * nparts * sizeof(float) + 2 * (size_t)cols * 64 * sizeof(float)));
+        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipLayerNormBackward: workspace allocation failed");
+        float* pdw = dW ? part : nullptr;
+        float* pdb = dB ? part + (dW ? pf : 0) : nullptr;
+        hipLaunchKernelGGL(layernorm_bwd_dwdb_cols, dim3((unsigned)col_blocks, (unsigned)ry), dim3(256), 0, st, dY, X, mean, rstd, pdw, pdb, rows, cols, rpb);
+        NNHIP_LAUNCH_CHECK("layernorm_bwd_dwdb_cols");
+        float* scr = part + pf * nparts;
+        if (dW) {
+            const ColsumPlan cp = colsum_plan(pdw, dW, ry, cols, cols);
+            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "nnhipLayerNormBackward: column-sum scratch too small");
+            if (int rc = colsum_run(cp, pdw, ry, cols, cols, dW, scr, st)) return rc;
+        }
+        if (dB) {
+            const ColsumPlan cp = colsum_plan(pdb, dB, ry, cols, cols);
+            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "nnhipLayerNormBackward: column-sum scratch too small");
+            if (int rc = colsum_run(cp, pdb, ry, cols, cols, dB, scr, st)) return rc;
+        }
+        return 0;
+    }
+    const bool vec = aligned16(dY) && aligned16(X) && aligned16(weight) && aligned16(dX) && aligned16(dX_addend) &&
+                     aligned16(dW) && aligned16(dB) && cols % 4 == 0;
+    // persistent grid = the blocks that are resident at once, each accumulating dw/db partials over its rows (nnhipRMSNormBackwardEx)
+    const int rpb = cols <= 1024 ? 4 : 1;
+    int64_t nblk = ceil_div(rows > 0 ? rows : 1, rpb);
+    int slots = 1024;
+    ROW_DISPATCH_SLOTS(layernorm_bwd_rows, cols, vec, slots);
+    if (slots < 1) slots = 1;
+    if (nblk > slots) nblk = slots;
+    const size_t part_floats = ((size_t)nblk * cols + 63) / 64 * 64;
+    bool deferred = false;
+    float* part = nullptr;
+    if (nparts) {
+        // inside Tensor.backward() the finishing column sums wait for the flush, in the RMSNorm queue (one launch per pass)
+        int rcq = 0;
+        part = colsum_partials(part_floats * nparts, nparts, fin_sw(cols, vec), vec, st, &deferred, &rcq);
+        if (rcq) return rcq;
+        if (!part) part = static_cast<float*>(workspace(part_floats * nparts * sizeof(float)));
+        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipLayerNormBackward: workspace allocation failed");
+    }
+    float* part_dw = dW ? part : nullptr;
+    float* part_db = dB ? part + (dW ? part_floats : 0) : nullptr;
+    ROW_DISPATCH_GRID(layernorm_bwd_rows, cols, vec, nblk, st, dY, X, weight, mean, rstd, dX, part_dw, part_db, rows, cols, dX_addend, row_streaming(rows, cols, cols));
+    NNHIP_LAUNCH_CHECK("layernorm_backward");
+    if (nparts == 0) return 0;
+    if (deferred) {
+        if (dW) colsum_queue(part_dw, dW, nblk, cols);
+        if (dB) colsum_queue(part_db, dB, nblk, cols);
+        return 0;
+    }
+    if (dW) return colsum_tall(part_dw, dW, part_db, dB, nblk, cols, vec, st);
+    return colsum_tall(part_db, dB, nullptr, nullptr, nblk, cols, vec, st);
 }
 
 // ---- CrossEntropy -------------------------------------------------------------------------------

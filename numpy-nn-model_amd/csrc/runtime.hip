@@ -151,6 +151,9 @@ static const char* device_error_text(unsigned code) {
                    "the W2 / b2 update of that step was skipped, the optimizer state is half-stepped";
         case NNHIP_DEVERR_LSTM_SHAPE:
             return "an LSTM recurrence kernel (recurrent.hip) was launched with a shape its variant cannot hold; its outputs were not written";
+        case NNHIP_DEVERR_KVCACHE_FULL:
+            return "a KV-cache kernel (attention_decode.hip) met a row whose cache_len leaves no room for the tokens to append "
+                   "(cache_len outside 0 .. Tmax - T); that row's cache and output were not written";
         default: return "unknown device error code";
     }
 }
@@ -176,7 +179,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 211; }
+extern "C" int nnhipVersion(void) { return 212; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 

@@ -128,6 +128,14 @@ _SIGNATURES = {
     "nnhipRMSNormForward": (ctypes.c_int, [P, P, P, P, P, P, c_int64, c_int64, c_float, c_void_p]),
     "nnhipRMSNormBackward": (ctypes.c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_void_p]),
     "nnhipRMSNormBackwardEx": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_void_p]),
+    "nnhipLayerNormForward": (ctypes.c_int, [P, P, P, P, P, P, c_int64, c_int64, c_float, c_void_p]),
+    "nnhipLayerNormBackward": (ctypes.c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_void_p]),
+    "nnhipLayerNormBackwardEx": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_void_p]),
+    "nnhipGELUForward": (ctypes.c_int, [P, P, c_int64, c_void_p]),
+    "nnhipGELUBackward": (ctypes.c_int, [P, P, P, c_int64, c_void_p]),
+    "nnhipAttentionDecodeWorkspace": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
+    "nnhipAttentionDecode": (ctypes.c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p]),
+    "nnhipKVCacheFill": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipFusedAdamWStep": (ctypes.c_int, [P, P, P, P, c_double, c_double, c_double, c_double, c_double, c_int32, c_int64, c_int32, c_float, c_void_p]),
     "nnhipCreateFusedOptimizer": (c_void_p, []),
     "nnhipDestroyFusedOptimizer": (ctypes.c_int, [c_void_p]),

@@ -9,7 +9,8 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPEmbedding as Embedding, HIPDropout as Dropout, HIPMultiHeadAttention as MultiHeadAttention,
                            HIPPositionalEncoding as PositionalEncoding, HIPBatchNorm2d as BatchNorm2d,
                            HIPLeakyReLU as LeakyReLU, HIPMaxPool2d as MaxPool2d, HIPMSELoss as MSELoss,
-                           HIPSigmoid as Sigmoid, HIPLSTM as LSTM)
+                           HIPSigmoid as Sigmoid, HIPLSTM as LSTM, HIPLayerNorm as LayerNorm, HIPGELU as GELU,
+                           HIPCausalSelfAttention as CausalSelfAttention, KVCache)
 
 
 class CrossEntropyLoss(HIPCrossEntropyLoss):

@@ -1,6 +1,6 @@
 """HIP-accelerated layers: one-to-one counterparts of neunet/nn/experimental/*
 (the reference's CUDA* classes are also exported as aliases of the HIP* ones)."""
-from .activations import (CUDAFusedSwishAndMul, CUDASoftmax, CUDASwish, HIPFusedSwishAndMul, HIPReLU,  # noqa: F401
+from .activations import (CUDAFusedSwishAndMul, CUDASoftmax, CUDASwish, HIPFusedSwishAndMul, HIPGELU, HIPReLU,  # noqa: F401
                           HIPSoftmax, HIPSwish)
 from .linear import CUDALinear, HIPLinear  # noqa: F401
 from .linear_swish import CUDALinearSwish, HIPLinearSwish  # noqa: F401
@@ -11,3 +11,5 @@ from .attention import HIPMultiHeadAttention  # noqa: F401
 from .embedding import HIPDropout, HIPEmbedding, HIPPositionalEncoding  # noqa: F401
 from .vision import HIPBatchNorm2d, HIPLeakyReLU, HIPMaxPool2d, HIPMSELoss, HIPSigmoid  # noqa: F401
 from .recurrent import HIPLSTM  # noqa: F401
+from .layernorm import HIPLayerNorm  # noqa: F401
+from .causal_attention import HIPCausalSelfAttention, KVCache  # noqa: F401

@@ -115,6 +115,48 @@ class HIPSwish(Module):
         return _HIPSwishTensor(out, [x, self.beta], "swish", device=x.device)
 
 
+# ------------------------------------------------------------------------------------------- GELU
+def hip_gelu_forward(x, out):
+    """GELU, tanh form (neunet/nn/activations.py:412-417) -> nnhipGELUForward."""
+    _check_arrays(x, out)
+    if x.shape != out.shape:
+        raise ValueError("Input and output shapes must match")
+    call_hip_function("nnhipGELUForward", out, contiguous(x), x.numel(), get_current_stream_ptr())
+    return out
+
+
+def hip_gelu_backward(grad_input, grad_output, x):
+    """The exact derivative of the tanh form (the reference's, activations.py:396-401, rounds its constants to six digits)."""
+    _check_arrays(grad_input, grad_output, x)
+    if not (grad_input.shape == grad_output.shape == x.shape):
+        raise ValueError("Shapes must match")
+    call_hip_function("nnhipGELUBackward", grad_input, contiguous(grad_output), contiguous(x), x.numel(), get_current_stream_ptr())
+    return grad_input
+
+
+class _HIPGELUTensor(Tensor):
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+
+        def grad_fn(x: Tensor, grad):
+            grad_input = x.xp.empty_like(x.data)
+            hip_gelu_backward(grad_input, grad, x.data)
+            x.apply_grad(grad_input)
+
+        self.grad_fn = grad_fn
+
+
+class HIPGELU(Module):
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        require_device_f32(x)
+        out = x.xp.empty_like(x.data)
+        hip_gelu_forward(x.data, out)
+        return _HIPGELUTensor(out, [x], "gelu", device=x.device)
+
+
 # -------------------------------------------------------------------------------- SwiGLU gate
 def hip_fused_swish_and_mul(x, out, beta: float = 1.0, hidden_size=None):
     """cuda_fused_swish_and_mul (fused_swish_and_mul.py:44-89): x rows = [gate | up]."""

@@ -38,6 +38,21 @@ def save(name, **arrays):
         print(f"{name:28s} {os.path.getsize(path) / 1024:8.1f} KiB")
 
 
+def save_parts(prefix, arrays, limit=900 * 1024):
+    """A dict of arrays too large for one committed file: packed in order into <prefix>_0.npz, <prefix>_1.npz, ... of at most
+    `limit` raw bytes each (random float32 data does not compress)."""
+    part, used, k = {}, 0, 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if part and used + a.nbytes > limit:
+            save(f"{prefix}_{k}", **part)
+            part, used, k = {}, 0, k + 1
+        part[name] = a
+        used += a.nbytes
+    if part:
+        save(f"{prefix}_{k}", **part)
+
+
 def seed_layers(n):
     """The reference layers draw their initial weights from the GLOBAL np.random (nn.Linear / Conv2d / Embedding
     __init__): seed it at the top of every generator so every fixture regenerates bit for bit
@@ -557,8 +572,197 @@ def gen_lstm():
     save("lstm_classifier", **arrs)
 
 
+# --------------------------------------------------------------------------- LayerNorm / GELU / GPT-2 (examples/gpt2/gpt2_infer.py)
+def gen_layernorm_gelu():
+    seed_layers(113)
+    rng = np.random.default_rng(23)
+    cases = [("layernorm_2d", (8, 64), 64, True), ("layernorm_3d", (2, 5, 48), 48, True),
+             ("layernorm_noaffine", (6, 40), 40, False), ("layernorm_shape2", (3, 4, 32), (4, 32), True)]
+    for tag, shape, nshape, affine in cases:
+        X = (rng.standard_normal(shape) * 1.5 + 0.3).astype(F32)
+        dY = rng.standard_normal(shape).astype(F32)
+        layer = nn.LayerNorm(nshape, eps=1e-5, elementwise_affine=affine)
+        arrs = dict(X=X, dY=dY, eps=np.float64(1e-5), normalized_shape=np.atleast_1d(np.array(nshape, np.int64)))
+        if affine:
+            assert np.all(layer.weight.data == 1) and not np.any(layer.bias.data)      # the initial values the HIP class must share
+            w = rng.uniform(0.5, 1.5, layer.weight.shape).astype(F32)
+            b = rng.uniform(-0.5, 0.5, layer.bias.shape).astype(F32)
+            layer.weight.data[...] = w
+            layer.bias.data[...] = b
+            arrs.update(w=w, b=b)
+        x = T(X)
+        y = layer(x)
+        y.backward(dY)
+        arrs.update(Y=y.data, dX=x.grad)
+        if affine:
+            # 3-D inputs: the reference sums dW over axis 0 only and apply_grad's reverse broadcast finishes -- the full sum is pinned
+            arrs.update(dw=layer.weight.grad, db=layer.bias.grad)
+            assert layer.weight.grad.shape == w.shape and layer.bias.grad.shape == b.shape
+        save(tag, **arrs)
+    X = np.concatenate([np.linspace(-6, 6, 97), rng.standard_normal(31) * 2]).reshape(8, 16).astype(F32)
+    dY = rng.standard_normal(X.shape).astype(F32)
+    x = T(X)
+    y = nn.GELU()(x)
+    y.backward(dY)
+    save("gelu", X=X, dY=dY, Y=y.data, dX=x.grad)
+
+
+GPT2_TINY_CFG = {"n_embd": 128, "n_head": 2, "n_layer": 2, "vocab_size": 512, "n_positions": 64, "layer_norm_epsilon": 1e-5}
+# Seed of the greedy fixture's weights: the first of 0, 1, 2, ... whose 32-token continuation meets BOTH conditions gen_gpt2 asserts
+# (every float64 top-1/top-2 margin >= 1e-3 of the step's largest |logit|, at least 8 distinct new tokens); found by
+# `python tools/gen_golden.py --search-gpt2-seed`.  Plain N(0, 0.02) weights collapse to repeating one to three tokens, hence the
+# larger positional and residual-branch scales below.
+GPT2_TINY_SEED = 0
+GPT2_TINY_SCALES = {"wte": 0.05, "wpe": 0.2, "attn": 0.12, "mlp": 0.12, "bias": 0.05}
+
+
+def _gpt2_script_namespace():
+    """exec() the model classes, the weight loader and the generation loop straight from the reference's
+    /root/reference/examples/gpt2/gpt2_infer.py (its hub / tokenizer imports are not needed and not executed) -- nothing of the
+    script is copied into this repository."""
+    import time
+    from dataclasses import dataclass
+    from typing import Any
+    src = open("/root/reference/examples/gpt2/gpt2_infer.py").read()
+    helpers = src[src.index("def _to_numpy"):src.index("def download_gpt2_files")]
+    body = src[src.index("class CausalSelfAttention"):src.index("class TransformersGPT2Runner")]
+    ns = {"nn": nn, "neunet": neunet, "Tensor": Tensor, "np": np, "Any": Any, "dataclass": dataclass, "time": time}
+    exec("from __future__ import annotations\n" + helpers + body, ns)
+    return ns
+
+
+def _gpt2_tiny_state(seed):
+    """A Hugging-Face-shaped state dict (Conv1D weights [in, out]) for GPT2_TINY_CFG."""
+    cfg, sc = GPT2_TINY_CFG, GPT2_TINY_SCALES
+    rng = np.random.default_rng(seed)
+    D, V, P = cfg["n_embd"], cfg["vocab_size"], cfg["n_positions"]
+    n = lambda scale, *s: (rng.standard_normal(s) * scale).astype(F32)  # noqa: E731
+    g = lambda *s: rng.uniform(0.7, 1.3, s).astype(F32)  # noqa: E731
+    sd = {"transformer.wte.weight": n(sc["wte"], V, D), "transformer.wpe.weight": n(sc["wpe"], P, D),
+          "transformer.ln_f.weight": g(D), "transformer.ln_f.bias": n(sc["bias"], D)}
+    for i in range(cfg["n_layer"]):
+        p = f"transformer.h.{i}."
+        sd.update({p + "ln_1.weight": g(D), p + "ln_1.bias": n(sc["bias"], D), p + "ln_2.weight": g(D), p + "ln_2.bias": n(sc["bias"], D),
+                   p + "attn.c_attn.weight": n(sc["attn"], D, 3 * D), p + "attn.c_attn.bias": n(sc["bias"], 3 * D),
+                   p + "attn.c_proj.weight": n(sc["attn"], D, D), p + "attn.c_proj.bias": n(sc["bias"], D),
+                   p + "mlp.c_fc.weight": n(sc["mlp"], D, 4 * D), p + "mlp.c_fc.bias": n(sc["bias"], 4 * D),
+                   p + "mlp.c_proj.weight": n(sc["mlp"], 4 * D, D), p + "mlp.c_proj.bias": n(sc["bias"], D)})
+    return sd
+
+
+def _gpt2_named_params(model):
+    """state_dict() plus lm_head.weight: the reference's loader leaves the head a plain Tensor CLONE of wte.weight (gpt2_infer.py:289),
+    which state_dict() and parameters() do not list -- it still takes part in the forward pass and receives a gradient."""
+    params = {k: np.asarray(v) for k, v in model.state_dict().items()}
+    assert "lm_head.weight" not in params
+    params["lm_head.weight"] = np.asarray(model.lm_head.weight.data)
+    return params
+
+
+class _IdTokenizer:
+    """Stands in for tokenizers.Tokenizer in the reference's generation loop: "text" is comma-separated token ids."""
+
+    class _Enc:
+        def __init__(self, ids):
+            self.ids = ids
+
+    def encode(self, text):
+        return self._Enc([int(t) for t in text.split(",")])
+
+    def decode(self, ids):
+        return ",".join(str(int(t)) for t in ids)
+
+
+def _gpt2_tiny_greedy(ns, seed, n_new=32):
+    """(model, state, prompt, the 8 + n_new tokens the REFERENCE's generate loop produces greedily, the float64 restatement's logits
+    of every position of that sequence)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from gpt2_ref import gpt2_forward
+    state = _gpt2_tiny_state(seed)
+    model = ns["GPT2"](dict(GPT2_TINY_CFG))
+    ns["load_gpt2_weights"](model, state)
+    model.eval()
+    prompt = np.random.default_rng(seed + 1000).integers(0, GPT2_TINY_CFG["vocab_size"], 8)
+    req = ns["GenerationRequest"](prompt=",".join(str(int(t)) for t in prompt), max_new_tokens=n_new, temperature=1.0, top_k=0)
+    res = ns["NeunetGPT2Runner"](model=model, tokenizer=_IdTokenizer()).generate(req)
+    tokens = np.array([int(t) for t in res.text.split(",")], dtype=np.int32)
+    params = _gpt2_named_params(model)
+    logits64, _ = gpt2_forward(params, tokens[None], GPT2_TINY_CFG["n_head"])
+    return model, state, prompt, tokens, logits64[0]
+
+
+def _gpt2_greedy_ok(tokens, logits64, n_new=32):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from gpt2_ref import greedy_margins
+    steps = logits64[len(tokens) - n_new - 1:len(tokens) - 1]            # position t predicts token t + 1
+    same = np.array_equal(np.argmax(steps, axis=-1), tokens[-n_new:])
+    return same, float(greedy_margins(steps).min()), len(set(tokens[-n_new:].tolist()))
+
+
+def search_gpt2_seed(limit=200):
+    ns = _gpt2_script_namespace()
+    for seed in range(limit):
+        seed_layers(114)
+        _, _, _, tokens, logits64 = _gpt2_tiny_greedy(ns, seed)
+        same, margin, distinct = _gpt2_greedy_ok(tokens, logits64)
+        print(f"seed {seed}: float64 picks the same tokens {same}, min margin {margin:.2e}, distinct {distinct}")
+        if same and margin >= 1e-3 and distinct >= 8:
+            return seed
+    raise SystemExit("no seed met the conditions")
+
+
+def gen_gpt2():
+    seed_layers(114)
+    ns = _gpt2_script_namespace()
+    cfg = GPT2_TINY_CFG
+    model, state, prompt, tokens, logits64 = _gpt2_tiny_greedy(ns, GPT2_TINY_SEED)
+    same, margin, distinct = _gpt2_greedy_ok(tokens, logits64)
+    # the fixture's conditions (tests/test_gpt2.py re-asserts them on the stored arrays); no step is exempt
+    assert same, "the float64 restatement picks other tokens than the reference's float32 loop"
+    assert margin >= 1e-3, f"greedy margin {margin:.2e} < 1e-3 of the step's largest |logit|"
+    assert distinct >= 8, f"only {distinct} distinct tokens in the continuation"
+    # one training-shaped pass: [2, 24] ids (with repeats), mean cross entropy against the next token, every parameter's gradient
+    rng = np.random.default_rng(24)
+    batch = rng.integers(0, cfg["vocab_size"], (2, 25)).astype(np.int32)
+    batch[0, 7] = batch[0, 3]
+    batch[1, 20] = batch[0, 3]
+    model.train()
+    out = model(batch[:, :-1])
+    logits = out.data.copy()
+    loss = nn.CrossEntropyLoss()(out.reshape(out.shape[0] * out.shape[1], out.shape[2]),
+                                 neunet.tensor(batch[:, 1:].flatten(), dtype=neunet.int32))
+    loss.backward()
+    by_name = _gpt2_named_params(model)
+    names = list(by_name)
+    arrs = dict(cfg=np.array([cfg["n_embd"], cfg["n_head"], cfg["n_layer"], cfg["vocab_size"], cfg["n_positions"]], np.int64),
+                seed=np.int64(GPT2_TINY_SEED), batch=batch, logits=logits, loss=np.float64(loss.data),
+                prompt=prompt.astype(np.int32), tokens=tokens, logits64=logits64, names=np.array(names))
+    grads = {}
+
+    def walk(mod, prefix):
+        for name, item in mod.__dict__.items():
+            if isinstance(item, Tensor) and item.__class__.__name__ == "Parameter":
+                grads[prefix + name] = item.grad
+            elif hasattr(item, "modules") and isinstance(item.modules, list):
+                for i, m in enumerate(item.modules):
+                    walk(m, f"{prefix}{name}.{i}.")
+            elif hasattr(item, "state_dict"):
+                walk(item, prefix + name + ".")
+
+    walk(model, "")
+    grads["lm_head.weight"] = model.lm_head.weight.grad
+    assert sorted(grads) == sorted(names), (sorted(set(names) ^ set(grads)))
+    save("gpt2_tiny", **arrs)
+    # the Hugging-Face-shaped checkpoint the reference's loader was given (the model's own arrays are its transposes: the tests
+    # rebuild them with the loader's key mapping), and the gradient of every parameter under the model's names
+    save_parts("gpt2_tiny_hf", state)
+    for k in names:
+        assert grads[k] is not None, k
+    save_parts("gpt2_tiny_grad", {k: np.asarray(grads[k]).reshape(np.shape(by_name[k])) for k in names})
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
-              gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm]
+              gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2]
 
 
 def generate_all(out_dir=None, quiet=False):
@@ -574,5 +778,9 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="write the fixtures here instead of tests/golden")
+    ap.add_argument("--search-gpt2-seed", action="store_true", help="print the first seed that meets gen_gpt2's conditions and stop")
     a = ap.parse_args()
+    if a.search_gpt2_seed:
+        print("GPT2_TINY_SEED =", search_gpt2_seed())
+        sys.exit(0)
     generate_all(a.out)
