@@ -14,7 +14,14 @@ generate(ids, max_new_tokens, temperature, top_k, mode):
   cached     prefill once, then one single-token step per new token on the KV cache (nnhipAttentionDecode), eager launches
   graph      the single-token step is captured into a hipGraph once and replayed; greedy: nnhipArgmaxF32 writes the next id into
              the buffer the next replay reads and the positional row is gathered by cache_len, so the host synchronises once, at
-             the end.  Sampling (top_k > 0) reads the logits on the host after every replay, as the eager modes do.
+             the end.  Sampling (top_k > 0) with sampler="host" reads the logits on the host after every replay, as the eager
+             modes do; with sampler="device" nnhipSampleTopK sits where the argmax does and the loop is the greedy one.
+
+sampler (top_k > 0 only; top_k == 0 is greedy either way):
+  host    the reference's choice in NumPy (argpartition, softmax, Generator.choice) on a host copy of the logits: one
+          synchronisation and a [B, vocab] transfer per token in every mode
+  device  neunet_hip.sample_top_k: the token at sequence position p (0-based, prompt included) of row b is drawn with the uniform
+          of (seed + p, b) in every mode -- the eager modes add p on the host, the captured step reads it from cache_len
 """
 import argparse
 import os
@@ -248,13 +255,16 @@ def _pick(last, temperature, top_k, rng):
 
 class GraphedDecodeStep:
     """One single-token step of `model` on `cache`, captured into a hipGraph: ids_buf [B,1] -> embedding (positional row gathered
-    by cache_len) -> the blocks -> ln_f -> lm_head -> logits; greedy: argmax -> ids_buf; cache_len += 1.  One stream, no parallel
-    branches.  kernel_nodes / graph_nodes: what graph.count_graph_nodes finds in the captured graph."""
+    by cache_len) -> the blocks -> ln_f -> lm_head -> logits; greedy: argmax -> ids_buf; cache_len += 1; device sampler: top-k
+    draw -> ids_buf.  One stream, no parallel branches.  kernel_nodes / graph_nodes: what graph.count_graph_nodes finds in the
+    captured graph."""
 
-    def __init__(self, model: GPT2, cache, greedy=True):
+    def __init__(self, model: GPT2, cache, greedy=True, sampler=None):
+        """sampler: None, or (top_k, temperature, seed): the step ends in nnhipSampleTopK instead of the argmax, drawing with the
+        uniform of (seed + cache_len, row) -- cache_len AFTER the step's advance, the position of the token being chosen."""
         import torch
         from neunet_hip.graph import count_graph_nodes
-        self.model, self.cache, self.greedy = model, cache, greedy
+        self.model, self.cache, self.greedy, self.sampler = model, cache, greedy and sampler is None, sampler
         B, D = cache.B, model.n_embd
         self.ids_buf = torch.zeros((B, 1), dtype=torch.int32, device="cuda")
         self._tok = torch.empty((B, 1, D), dtype=torch.float32, device="cuda")
@@ -295,6 +305,10 @@ class GraphedDecodeStep:
         if self.greedy:
             call_hip_function("nnhipArgmaxF32", self.ids_buf, self.logits, c.B, m.vocab_size, 1, st())
         c.advance(1)
+        if self.sampler is not None:
+            # after the advance: cache_len[0] is now the position of the token this step chooses (rows advance in lockstep)
+            top_k, temperature, seed = self.sampler
+            neunet_hip.sample_top_k(self.logits[:, 0], top_k, temperature, seed=seed, seed_dev=c.cache_len, out=self.ids_buf)
 
     def replay(self):
         self.cache.replayed(1)
@@ -321,11 +335,14 @@ def _sync_clock():
     return time.perf_counter()
 
 
-def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="cached", seed=None, stats=None):
+def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="cached", seed=None, stats=None, sampler="host"):
     """ids: int array [B, T0] (or [T0]).  Returns int32 [B, T0 + max_new_tokens].  temperature / top_k as in the reference script
-    (top_k == 0: greedy).  stats (a dict, optional) receives what the run did: host synchronisations between tokens, replays,
-    graph node counts, and prefill_s / capture_s / decode_s, the seconds of the prefill, of the graph warm-up + capture and of the
-    token loop (the last new token's choice included)."""
+    (top_k == 0: greedy).  sampler: who draws when top_k > 0, "host" (NumPy on a copy of the logits) or "device"
+    (neunet_hip.sample_top_k, seeded per position: see the module docstring).  stats (a dict, optional) receives what the run did:
+    host synchronisations between tokens, replays, graph node counts, and prefill_s / capture_s / decode_s, the seconds of the
+    prefill, of the graph warm-up + capture and of the token loop (the last new token's choice included)."""
+    if sampler not in ("host", "device"):
+        raise ValueError(f"unknown sampler {sampler!r} (host, device)")
     import torch
     ids = np.atleast_2d(np.asarray(ids, dtype=np.int32))
     B, T0 = ids.shape
@@ -335,6 +352,20 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
         raise ValueError(f"{T0} + {max_new_tokens} tokens exceed n_positions = {model.n_positions}")
     rng = np.random.default_rng(seed)
     greedy = top_k <= 0
+    device_draw = sampler == "device" and not greedy
+    seed0 = int(seed or 0)
+
+    def draw(logits, p, out=None):
+        """The device sampler on the last position's logits, for the token at sequence position p."""
+        return neunet_hip.sample_top_k(logits.data[:, -1], top_k, temperature, seed=seed0 + p, out=out)
+
+    def pick_rows(logits, p):
+        """The next id of every row as a host array: the one transfer per token of the eager modes."""
+        if device_draw:
+            return draw(logits, p).cpu().numpy().astype(np.int32)
+        last = logits.data[:, -1].cpu().numpy()
+        return np.array([_pick(last[b], temperature, top_k, rng) for b in range(B)], dtype=np.int32)
+
     stats = stats if stats is not None else {}
     stats.update({"mode": mode, "host_syncs_between_tokens": 0, "replays": 0})
     was_training = model.training
@@ -345,9 +376,8 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
             t_loop = _sync_clock()
             for _ in range(max_new_tokens):
                 logits = model(seq)
-                last = logits.data[:, -1].cpu().numpy()
+                nxt = pick_rows(logits, seq.shape[1])
                 stats["host_syncs_between_tokens"] += 1
-                nxt = np.array([_pick(last[b], temperature, top_k, rng) for b in range(B)], dtype=np.int32)
                 seq = np.concatenate([seq, nxt[:, None]], axis=1)
             stats["decode_s"] = _sync_clock() - t_loop
             return seq
@@ -363,9 +393,8 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
             seq = ids.copy()
             t_loop = _sync_clock()
             for i in range(max_new_tokens):
-                last = logits.data[:, -1].cpu().numpy()
+                nxt = pick_rows(logits, T0 + i)
                 stats["host_syncs_between_tokens"] += 1
-                nxt = np.array([_pick(last[b], temperature, top_k, rng) for b in range(B)], dtype=np.int32)
                 seq = np.concatenate([seq, nxt[:, None]], axis=1)
                 if i + 1 < max_new_tokens:
                     logits = model(nxt[:, None], cache=cache)
@@ -373,15 +402,18 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
             return seq
         # graph: the first new id comes from the prefill's logits; every later one from a replay of the captured step
         t_setup = _sync_clock()
-        step = GraphedDecodeStep(model, cache, greedy=greedy)
+        step = GraphedDecodeStep(model, cache, greedy=greedy, sampler=(top_k, temperature, seed0) if device_draw else None)
         stats["kernel_nodes"], stats["graph_nodes"] = step.kernel_nodes, step.graph_nodes
         out = torch.empty((B, max_new_tokens), dtype=torch.int32, device="cuda")
         t_loop = _sync_clock()
         stats["capture_s"] = t_loop - t_setup
         try:
-            if greedy:
-                call_hip_function("nnhipArgmaxF32", step.ids_buf, logits.data[:, -1].contiguous(), B, model.vocab_size, 1,
-                                  get_current_stream_ptr())
+            if greedy or device_draw:
+                if greedy:
+                    call_hip_function("nnhipArgmaxF32", step.ids_buf, logits.data[:, -1].contiguous(), B, model.vocab_size, 1,
+                                      get_current_stream_ptr())
+                else:
+                    draw(logits, T0, out=step.ids_buf)                     # the first new token: from the prefill's logits
                 out[:, 0:1].copy_(step.ids_buf)                            # stream-ordered device copies: no host involvement
                 for i in range(1, max_new_tokens):
                     step.replay()
@@ -418,7 +450,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--max-new-tokens", type=int, default=50)
     ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--top-k", type=int, default=0, help="0 = greedy (the reference script's default is 40)")
+    ap.add_argument("--top-k", type=int, default=0, help="0 = greedy; the reference script's default is 40: pass --top-k 40, with "
+                    "--sampler device to keep the graph mode free of host synchronisations (tokens then differ from --sampler host: "
+                    "another random stream)")
+    ap.add_argument("--sampler", default="host", choices=["host", "device"], help="who draws when --top-k > 0: NumPy on a host copy of "
+                    "the logits (one synchronisation per token), or nnhipSampleTopK on the device")
     ap.add_argument("--mode", default="graph", choices=["recompute", "cached", "graph"])
     a = ap.parse_args()
     if not a.random and not a.weights:
@@ -446,7 +482,7 @@ def main():
     stats = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = generate(model, ids, a.max_new_tokens, a.temperature, a.top_k, a.mode, seed=a.seed, stats=stats)
+    out = generate(model, ids, a.max_new_tokens, a.temperature, a.top_k, a.mode, seed=a.seed, stats=stats, sampler=a.sampler)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     for row in out:

@@ -670,6 +670,26 @@ int nnhipAttentionDecode(const float* qkv, float* Kcache, float* Vcache, const i
 int nnhipKVCacheFill(const float* qkv, float* Kcache, float* Vcache, const int32_t* cache_len, int64_t B, int64_t H, int64_t T,
                      int64_t Tmax, int64_t head_dim, int64_t ld_qkv, nnhipStream_t stream);
 
+/* ---- device-side top-k sampling (net-new export, ABI 213; csrc/sample.hip) ---------------------------------------------------------
+ * Replaces the host-side choice of the next token in the reference's GPT-2 script (examples/gpt2/gpt2_infer.py:331-338: last /
+ * max(temperature, 1e-6), np.argpartition, softmax_np, np.random.choice), which needs the whole row of logits on the host.
+ *   logits  [rows, n], row stride ld >= n floats (rows need not be 16-byte aligned);  out_ids int32 [rows];
+ *   u_out   NULL, or float [rows]: receives the uniform each row used.
+ * Row r.  Candidates: the k = min(top_k, n) best elements under nnhipArgmaxF32's total order (a NaN beats any number, a larger
+ * value beats a smaller one, ties go to the lower index -- which also decides which of several equal values at the k-th place
+ * belong), sorted by that order: x_0 is the argmax.  t = max(temperature, 1e-6); e_j = exp((x_j - x_0) / t) in float32;
+ * c_j = e_0 + ... + e_j summed sequentially in sorted order.  s = seed + (seed_dev ? *seed_dev : 0) mod 2^32;
+ * u = (hash(s, r) >> 8) * 2^-24 in [0, 1), the counter-based hash of nnhipDropout / the attention dropout with key 0.
+ * out_ids[r] = index of the first sorted candidate with c_j > u * c_{k-1}; if rounding leaves none, the last one with e_j > 0.
+ * If x_0 is NaN or not finite, out_ids[r] is its index (argmax's answer); -inf logits are legal otherwise and are never drawn.
+ * Bit-identical from run to run.  seed_dev (optional DEVICE uint32, e.g. a position counter) is read inside the kernel, so a
+ * captured hipGraph draws a fresh token on every replay.  At most two kernel launches and nothing else; partial results go through
+ * the library workspace (reserve or warm up before capturing).  top_k outside 1 .. NNHIP_SAMPLE_MAX_K, temperature NaN or
+ * negative, ld < n, n >= 2^31, n < 1 or a null out_ids / logits with rows > 0: NNHIP_EINVAL.  rows == 0: returns 0. */
+#define NNHIP_SAMPLE_MAX_K 1024
+int nnhipSampleTopK(int32_t* out_ids, float* u_out, const float* logits, int64_t rows, int64_t n, int64_t ld, int32_t top_k,
+                    float temperature, uint32_t seed, const uint32_t* seed_dev, nnhipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,15 +79,8 @@ struct AttnBwdParams {
 __device__ __forceinline__ int acc_row(int e, int lh) { return (e & 3) + 8 * (e >> 2) + 4 * lh; }
 
 // ---- dropout multiplier of element (row = (b*H + h)*Tq + q, key) ------------------------------------------------------
-// lowbias32-style integer hash of (seed, row, key): cheap enough (~10 VALU) to re-evaluate in all three kernels.
-__device__ __forceinline__ unsigned at_rowkey(unsigned seed, unsigned row) { return (seed * 0x85EBCA6Bu + 0x9E3779B9u) ^ (row * 0xC2B2AE35u); }
-__device__ __forceinline__ unsigned at_hash(unsigned rowkey, unsigned key) {
-    unsigned x = rowkey ^ (key * 0x9E3779B1u);
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
+// at_rowkey / at_hash (common.h): the lowbias32-style hash of (seed, row, key), cheap enough (~10 VALU) to re-evaluate in all
+// three kernels.
 // the device-side seed offset: an agent-scope (L2-served) load, NOT a scalar load -- the word is rewritten between launches
 // by other kernels and a scalar-cache line of it was observed stale on some CUs
 __device__ __forceinline__ unsigned at_seed_offset(const AttnExtra& x) {

@@ -170,6 +170,17 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 __device__ __forceinline__ float ld_dev_f32(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int ld_dev_i32(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// Counter-based random bits: a lowbias32-style integer hash of (seed, row, key).  The fused attention's dropout evaluates it per
+// (query row, key); nnhipSampleTopK (sample.hip) draws a row's uniform from key 0.  One definition: both must see the same bits.
+__device__ __forceinline__ unsigned at_rowkey(unsigned seed, unsigned row) { return (seed * 0x85EBCA6Bu + 0x9E3779B9u) ^ (row * 0xC2B2AE35u); }
+__device__ __forceinline__ unsigned at_hash(unsigned rowkey, unsigned key) {
+    unsigned x = rowkey ^ (key * 0x9E3779B1u);
+    x ^= x >> 16; x *= 0x7FEB352Du;
+    x ^= x >> 15; x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
 constexpr float kLog2e = 1.4426950408889634f;
 // exp(x) for x <= ~0 as one v_exp_f32 (1 ulp) after a multiply: softmax / log-sum-exp terms exp(x - max).
 __device__ __forceinline__ float exp_fast_(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }

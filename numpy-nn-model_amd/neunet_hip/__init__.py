@@ -56,6 +56,57 @@ def argmax(x: Tensor, axis=None, keepdims=False):
     return Tensor(out, dtype=np.int32, requires_grad=False, device="cuda")
 
 
+SAMPLE_MAX_K = 1024      # NNHIP_SAMPLE_MAX_K (include/neunet_hip.h)
+
+
+def sample_top_k(logits, top_k, temperature=1.0, seed=0, seed_dev=None, out=None, return_u=False):
+    """Draw one id per row of `logits` [..., n] on the device (nnhipSampleTopK): temperature, top-k and the multinomial draw of the
+    reference's GPT-2 script (examples/gpt2/gpt2_infer.py:331-338) without a host copy of the logits.  logits: a device Tensor or
+    torch tensor, float32, unit stride along the last axis; the leading axes may sit in a wider buffer (one row stride, passed as
+    ld).  The row's uniform is a hash of (seed + *seed_dev, row): seed_dev is an optional device int32 / uint32 word (its first
+    element is read inside the kernel, so a captured hipGraph draws afresh on every replay).  Returns the int32 ids (a device
+    torch tensor of shape logits.shape[:-1], or `out`, which only needs that many int32 elements); with return_u also the float32
+    uniforms each row used.  top_k < 1 is a ValueError: greedy decoding is argmax."""
+    top_k = int(top_k)
+    if top_k < 1:
+        raise ValueError(f"sample_top_k needs top_k >= 1 (got {top_k}); greedy decoding is neunet_hip.argmax")
+    if top_k > SAMPLE_MAX_K:
+        raise ValueError(f"sample_top_k supports top_k <= {SAMPLE_MAX_K} (got {top_k})")
+    temperature = float(temperature)
+    if not temperature >= 0.0:
+        raise ValueError(f"sample_top_k needs a temperature >= 0 (got {temperature})")
+    import torch
+    from ._lib import StridedView, call_hip_function, get_current_stream_ptr
+    d = logits.data if isinstance(logits, Tensor) else logits
+    if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float32:
+        raise ValueError("sample_top_k needs float32 logits on the device")
+    if d.dim() < 1 or d.shape[-1] < 1:
+        raise ValueError("sample_top_k needs a last axis of at least one element")
+    n, lead = d.shape[-1], tuple(d.shape[:-1])
+    rows = int(np.prod(lead, dtype=np.int64))
+    ld = n
+    if not d.is_contiguous():
+        # one row stride for all leading axes (e.g. logits[:, -1] of [B, T, n]); anything else would need a copy: refuse
+        axes = [(d.shape[i], d.stride(i)) for i in range(d.dim() - 1) if d.shape[i] > 1]
+        ld = axes[-1][1] if axes else n
+        ok = d.stride(-1) == 1 and ld >= n
+        for (_, s0), (n1, s1) in zip(axes[:-1], axes[1:]):
+            ok = ok and s0 == s1 * n1
+        if not ok:
+            raise ValueError("sample_top_k needs unit stride along the last axis and one row stride >= n for the leading axes")
+    if seed_dev is not None and not (isinstance(seed_dev, torch.Tensor) and seed_dev.is_cuda and seed_dev.numel() >= 1
+                                     and seed_dev.dtype in (torch.int32, torch.uint32)):
+        raise ValueError("seed_dev must be a device int32 / uint32 tensor")
+    if out is None:
+        out = torch.empty(lead, dtype=torch.int32, device=d.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.numel() == rows and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous device int32 tensor of {rows} elements")
+    u = torch.empty(lead, dtype=torch.float32, device=d.device) if return_u else None
+    call_hip_function("nnhipSampleTopK", out, u, StridedView(d), rows, n, ld, top_k, temperature, int(seed) & 0xFFFFFFFF, seed_dev,
+                      get_current_stream_ptr())
+    return (out, u) if return_u else out
+
+
 def save(obj, path):
     """neunet.save = pickle (neunet/__init__.py:26-29)."""
     import pickle

@@ -13,7 +13,11 @@
               number of bytes: read-only (torch.sum) and 1 read + 1 write (nnhipReLUForward).
   rows        nn.LayerNorm and nn.GELU kernels at [16384, 768] and [16384, 3072], forward and backward.
   generate    tokens/s of the three modes of examples/gpt2_infer.py (prompt 128, 128 new tokens, B 1 and 32, random weights), beside
-              the floor of streaming every parameter once per step at the measured stream rate.
+              the floor of streaming every parameter once per step at the measured stream rate; then top_k 40 in graph mode with
+              the host sampler (a synchronisation and a [B, vocab] transfer per token) and the device sampler (nnhipSampleTopK
+              inside the captured step).
+  sampler     one nnhipSampleTopK call (top_k 40) beside one nnhipArgmaxF32 call on the same [B, 50257] logits, B 1 and 32: both
+              read every logit once.
   families    (a rocprofv3 run of its own, then a summary) device time per kernel family of B = 1 graph-replayed decode steps:
               Linear, attention, norms / activations / embedding, the gaps between kernels, and Linear's distance from streaming
               every weight once.
@@ -155,7 +159,8 @@ def bench_generate(stream_GBps):
     import numpy as np
     G, model = build_model()
     pb = param_bytes(model)
-    res = {"param_bytes": pb, "stream_GBps": stream_GBps, "floor_ms_per_step": round(pb / stream_GBps / 1e6, 4), "runs": []}
+    res = {"param_bytes": pb, "stream_GBps": stream_GBps, "floor_ms_per_step": round(pb / stream_GBps / 1e6, 4), "runs": [],
+           "sampled_runs": []}
     rng = np.random.default_rng(1)
     for B in (1, 32):
         ids = rng.integers(0, G.GPT2_SMALL["vocab_size"], (B, 128)).astype(np.int32)
@@ -175,6 +180,33 @@ def bench_generate(stream_GBps):
                                 "kernel_nodes": stats.get("kernel_nodes")})
         res[f"same_tokens_B{B}"] = bool(np.array_equal(toks["cached"], toks["graph"]))
         res[f"recompute_matches_cached_B{B}"] = float(np.mean(toks["cached"] == toks["recompute"]))
+        for sampler in ("host", "device"):                            # the reference script's default: top_k 40
+            G.generate(model, ids, 4, top_k=40, mode="graph", seed=0, sampler=sampler)
+            stats = {}
+            t0 = time.perf_counter()
+            G.generate(model, ids, 128, top_k=40, mode="graph", seed=0, stats=stats, sampler=sampler)
+            wall = time.perf_counter() - t0
+            res["sampled_runs"].append({"B": B, "mode": "graph", "top_k": 40, "sampler": sampler, "wall_s": round(wall, 4),
+                                        "tokens_per_s_end_to_end": round(B * 128 / wall, 1), "decode_s": round(stats["decode_s"], 4),
+                                        "ms_per_step": round(stats["decode_s"] / 127 * 1e3, 4),
+                                        "tokens_per_s_token_loop": round(B * 127 / stats["decode_s"], 1),
+                                        "host_syncs_between_tokens": stats["host_syncs_between_tokens"],
+                                        "kernel_nodes": stats.get("kernel_nodes"), "graph_nodes": stats.get("graph_nodes")})
+    return res
+
+
+def bench_sampler(reps):
+    import torch
+    import neunet_hip
+    from neunet_hip import _lib
+    st = _lib.get_current_stream_ptr
+    res = []
+    for B in (1, 32):
+        x = torch.randn((B, 50257), device="cuda") * 3
+        out = torch.empty((B,), dtype=torch.int32, device="cuda")
+        us_arg = event_median(lambda: _lib.call_hip_function("nnhipArgmaxF32", out, x, B, 50257, 1, st()), reps)
+        us_smp = event_median(lambda: neunet_hip.sample_top_k(x, 40, 0.9, seed=1, out=out), reps)
+        res.append({"B": B, "n": 50257, "top_k": 40, "argmax_us": round(us_arg, 2), "sample_top_k_us": round(us_smp, 2)})
     return res
 
 
@@ -185,7 +217,7 @@ def family_of(name):
         return "attention"
     if n.startswith(("gemm_", "sg_", "splitk_", "colsum_")):           # every Linear: the GEMM kernels and their reduces / bias sums
         return "linear"
-    if n.startswith(("layernorm_", "map1_kernel", "map2_kernel", "embedding_", "argmax_", "at::native")):
+    if n.startswith(("layernorm_", "map1_kernel", "map2_kernel", "embedding_", "argmax_", "sample_", "at::native")):
         return "norm_act_embed"                                        # (at::native: torch's cache_len += 1)
     return "other"
 
@@ -244,6 +276,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--skip-generate", action="store_true")
+    ap.add_argument("--only", default=None, choices=["sampler", "generate"], help="only this section (generate: with the read-stream rate "
+                    "given by --stream-GBps instead of the attention section's measurement)")
+    ap.add_argument("--stream-GBps", type=float, default=0.0)
     ap.add_argument("--families-run", type=int, default=0, metavar="STEPS", help="only the workload of the per-family profile")
     ap.add_argument("--families-summary", nargs=3, metavar=("KERNEL_STATS_CSV", "BENCH_JSON", "STEPS"),
                     help="summarise rocprofv3's kernel stats of a --families-run (no device needed)")
@@ -257,7 +292,16 @@ def main():
     if a.families_run:
         families_run(a.families_run)
         return
-    res = {"H": H, "dh": DH, "Tmax": TMAX, "layers_cycled": LAYERS, "attention": bench_attention(a.reps), "rows": bench_rows(a.reps)}
+    if a.only:
+        res = {"sampler": bench_sampler(a.reps)}
+        if a.only == "generate":
+            if a.stream_GBps <= 0:
+                raise SystemExit("--only generate needs --stream-GBps (the read-only stream rate the weight-stream floor is computed from)")
+            res["generate"] = bench_generate(a.stream_GBps)
+        print(json.dumps(res))
+        return
+    res = {"H": H, "dh": DH, "Tmax": TMAX, "layers_cycled": LAYERS, "attention": bench_attention(a.reps), "rows": bench_rows(a.reps),
+           "sampler": bench_sampler(a.reps)}
     if not a.skip_generate:
         big = max(r["read_stream_GBps"] for r in res["attention"])      # the read-only stream at the largest footprint
         res["generate"] = bench_generate(big)
