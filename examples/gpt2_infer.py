@@ -22,6 +22,13 @@ sampler (top_k > 0 only; top_k == 0 is greedy either way):
           synchronisation and a [B, vocab] transfer per token in every mode
   device  neunet_hip.sample_top_k: the token at sequence position p (0-based, prompt included) of row b is drawn with the uniform
           of (seed + p, b) in every mode -- the eager modes add p on the host, the captured step reads it from cache_len
+
+linear (cached and graph modes; recompute ignores it):
+  gemm    every Linear on the tiled MFMA GEMM (the default: the tokens of existing seeds stay what they are)
+  gemv    the run happens under neunet_hip.linear_gemv(): every Linear forward of 1..8 rows -- the single-token steps up to batch 8,
+          the graph mode's warm-up and capture included, and a prefill of at most 8 rows -- streams its weights once through
+          nnhipLinearGemvForward's kernel, one launch and no split-K reduce.  Another summation order: logits move in their last
+          bits.  The switch is back at its previous value when generate returns.
 """
 import argparse
 import os
@@ -335,14 +342,27 @@ def _sync_clock():
     return time.perf_counter()
 
 
-def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="cached", seed=None, stats=None, sampler="host"):
+def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="cached", seed=None, stats=None, sampler="host",
+             linear="gemm"):
     """ids: int array [B, T0] (or [T0]).  Returns int32 [B, T0 + max_new_tokens].  temperature / top_k as in the reference script
     (top_k == 0: greedy).  sampler: who draws when top_k > 0, "host" (NumPy on a copy of the logits) or "device"
-    (neunet_hip.sample_top_k, seeded per position: see the module docstring).  stats (a dict, optional) receives what the run did:
-    host synchronisations between tokens, replays, graph node counts, and prefill_s / capture_s / decode_s, the seconds of the
-    prefill, of the graph warm-up + capture and of the token loop (the last new token's choice included)."""
+    (neunet_hip.sample_top_k, seeded per position: see the module docstring).  linear: "gemm" or "gemv" (module docstring).  stats (a
+    dict, optional) receives what the run did: host synchronisations between tokens, replays, graph node counts, the linear setting,
+    and prefill_s / capture_s / decode_s, the seconds of the prefill, of the graph warm-up + capture and of the token loop (the last
+    new token's choice included)."""
     if sampler not in ("host", "device"):
         raise ValueError(f"unknown sampler {sampler!r} (host, device)")
+    if linear not in ("gemm", "gemv"):
+        raise ValueError(f"unknown linear {linear!r} (gemm, gemv)")
+    stats = stats if stats is not None else {}
+    stats["linear"] = linear
+    if linear == "gemv" and mode in ("cached", "graph"):
+        with neunet_hip.linear_gemv(True):
+            return _generate(model, ids, max_new_tokens, temperature, top_k, mode, seed, stats, sampler)
+    return _generate(model, ids, max_new_tokens, temperature, top_k, mode, seed, stats, sampler)
+
+
+def _generate(model, ids, max_new_tokens, temperature, top_k, mode, seed, stats, sampler):
     import torch
     ids = np.atleast_2d(np.asarray(ids, dtype=np.int32))
     B, T0 = ids.shape
@@ -366,7 +386,6 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
         last = logits.data[:, -1].cpu().numpy()
         return np.array([_pick(last[b], temperature, top_k, rng) for b in range(B)], dtype=np.int32)
 
-    stats = stats if stats is not None else {}
     stats.update({"mode": mode, "host_syncs_between_tokens": 0, "replays": 0})
     was_training = model.training
     model.eval()
@@ -438,7 +457,7 @@ def generate(model: GPT2, ids, max_new_tokens, temperature=1.0, top_k=0, mode="c
         model.train(was_training)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--weights", default=None, help="local pytorch_model.bin or model.safetensors")
     ap.add_argument("--random", action="store_true", help="GPT-2-small-shaped random weights")
@@ -456,6 +475,13 @@ def main():
     ap.add_argument("--sampler", default="host", choices=["host", "device"], help="who draws when --top-k > 0: NumPy on a host copy of "
                     "the logits (one synchronisation per token), or nnhipSampleTopK on the device")
     ap.add_argument("--mode", default="graph", choices=["recompute", "cached", "graph"])
+    ap.add_argument("--linear", default="gemm", choices=["gemm", "gemv"], help="cached / graph: gemv streams the weights of every Linear "
+                    "forward of 1..8 rows through the GEMV kernel (one launch, no split-K reduce; logits move in their last bits)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     if not a.random and not a.weights:
         ap.error("give --weights PATH or --random")
@@ -482,7 +508,8 @@ def main():
     stats = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = generate(model, ids, a.max_new_tokens, a.temperature, a.top_k, a.mode, seed=a.seed, stats=stats, sampler=a.sampler)
+    out = generate(model, ids, a.max_new_tokens, a.temperature, a.top_k, a.mode, seed=a.seed, stats=stats, sampler=a.sampler,
+                   linear=a.linear)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     for row in out:

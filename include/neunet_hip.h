@@ -74,8 +74,9 @@ int nnhipGetGemmMode(void);
 int nnhipSetGemmLockstep(int enable);
 int nnhipGetGemmLockstep(void);
 /* Launches since the library was loaded, per GEMM kernel family: 0 = classic fp32 128x128 tiles (gemm_f32_kernel),
- * 1 = persistent fp32 (gemm_pst_kernel), 2 = small-problem kernel (gemm_small*), 3 = split-bf16 (gemm_bf3_kernel);
- * -1 for any other argument.  Host-side bookkeeping for tests that must know which kernel produced a result.  ABI 203 */
+ * 1 = persistent fp32 (gemm_pst_kernel), 2 = small-problem kernel (gemm_small*), 3 = split-bf16 (gemm_bf3_kernel),
+ * 4 = the weight-streaming Linear forward for 1..8 rows (linear_gemv_kernel, ABI 214); -1 for any other argument.  Host-side
+ * bookkeeping for tests that must know which kernel produced a result.  ABI 203 */
 int64_t nnhipGemmLaunchCount(int family);
 
 /* ---- a1/a2 Linear  (replaces cudaLinearModuleForward/Backward,
@@ -99,6 +100,28 @@ int nnhipLinearModuleForwardEx(const float* X, const float* W, const float* b, c
 int nnhipLinearModuleBackwardEx(const float* X, const float* W, const float* dO, const float* dX_addend, float* dX,
                                 float* dW, float* db, int64_t rows, int64_t in_features, int64_t out_features,
                                 nnhipStream_t stream);
+
+/* Weight-streaming forward for a handful of rows (extension, ABI 214; no reference counterpart): the single-token steps of
+ * KV-cached decoding, where a 128x128-tile GEMM is 127/128 empty and needs a split-K reduce behind it.
+ *   O[r,n] = sum_k X[r,k]*W[n,k] (+ b[n]) (+ addend[r,n]),   0 <= rows <= NNHIP_LINEAR_GEMV_MAX_ROWS; b and addend may be NULL;
+ *   addend under the aliasing contract of nnhipLinearModuleForwardEx.
+ * One kernel launch, no workspace, exact fp32 on the vector ALU; every weight is read once and used for all rows.  Results are
+ * bit-identical from run to run, and the bits of O[r,:] depend on X[r,:], W, b and addend[r,:] only: row r of an 8-row call equals
+ * a 1-row call on that row.  The epilogue is (acc + b[n]) + addend[r,n], each step rounded.  Any in_features / out_features;
+ * 4-byte alignment is enough (16-byte loads are used when in_features % 4 == 0 and X, W are 16-byte aligned).
+ * This entry always runs the kernel.  NNHIP_EINVAL: rows > NNHIP_LINEAR_GEMV_MAX_ROWS, a negative size, a null X, W or O with work
+ * to do; NNHIP_EALIGN: any pointer not 4-byte aligned.  rows == 0 or out_features == 0: returns 0, launches nothing;
+ * in_features == 0: what nnhipLinearModuleForwardEx does for the same arguments. */
+#define NNHIP_LINEAR_GEMV_MAX_ROWS 8
+int nnhipLinearGemvForward(const float* X, const float* W, const float* b, const float* addend, float* O, int64_t rows,
+                           int64_t in_features, int64_t out_features, nnhipStream_t stream);
+/* Process-wide switch, 0 (default) or 1; anything else is NNHIP_EINVAL and changes nothing.  While it is 1,
+ * nnhipLinearModuleForward and nnhipLinearModuleForwardEx with 1 <= rows <= NNHIP_LINEAR_GEMV_MAX_ROWS run the kernel above, in
+ * either GEMM mode (small problems stay exact fp32).  Off by default because another summation order moves results in their last
+ * bits.  Every other entry -- the activation-fused forwards, LinearSwish, every backward -- ignores it.  ABI 214 */
+int nnhipSetLinearGemv(int enable);
+/* The current value of the switch. */
+int nnhipGetLinearGemv(void);
 
 /* Deferred parameter gradients (extension; the reference computes each layer's dW where its backward runs, linear.py:17-24).
  * enable != 0: from now on the Linear backward entry points (nnhipLinearModuleBackward[Ex|Act], nnhipLinearSwishBackward) QUEUE

@@ -532,7 +532,9 @@ int gemm_f32_ex(const float* A, const float* B, float* C, const float* bias, flo
 // gemm_bf3.hip: the same tiles on the bf16 matrix cores (exact 3-way bf16 split of every fp32 operand, 6 products)
 int gemm_bf3_launch(const GemmParams& p, bool a_kmajor, bool b_kmajor, bool vec, bool cs, int64_t batch, hipStream_t st);
 int gemm_bf3_group_launch(const GemmGroup& g, int blocks, hipStream_t st);
-// launches per kernel family since load (nnhipGemmLaunchCount): 0 classic fp32 128x128, 1 persistent fp32, 2 small, 3 split-bf16.
+long long linear_gemv_launches();      // linear_gemv.hip
+// launches per kernel family since load (nnhipGemmLaunchCount): 0 classic fp32 128x128, 1 persistent fp32, 2 small, 3 split-bf16,
+// 4 the weight-streaming Linear forward for 1..8 rows (counted where it is launched, linear_gemv.hip).
 // Host-side counters for tests that must know WHICH kernel produced a result (a "bf16x3" test that only ever reaches the
 // small kernel proves nothing about gemm_bf3_kernel).
 static int gemm_f32_uneven_split(const float* A, const float* B, float* C, float* asum, int64_t M, int64_t N, int64_t K, int64_t lda,
@@ -910,6 +912,7 @@ extern "C" int nnhipSetGemmLockstep(int enable) {
 }
 extern "C" int nnhipGetGemmLockstep(void) { return nnhip::g_gemm_lockstep; }
 extern "C" int64_t nnhipGemmLaunchCount(int family) {
+    if (family == 4) return (int64_t)nnhip::linear_gemv_launches();
     return family >= 0 && family < 4 ? (int64_t)nnhip::g_gemm_launches[family] : -1;
 }
 

@@ -37,6 +37,8 @@ int gemm_small_mlp_backward_adam(const float* X1, const float* H, const float* W
 int colsum(const float* X, int64_t rows, int64_t cols, int64_t ld, float* out, hipStream_t st);
 int swish_backward_inplace(float* z_inout, const float* dY, float beta, int64_t n, hipStream_t st);
 int fill_f32(float* p, float v, int64_t n, hipStream_t st);
+int linear_gemv(const float* X, const float* W, const float* b, const float* addend, float* O, int64_t rows, int64_t in, int64_t out,
+                hipStream_t st);                                                            // linear_gemv.hip
 enum { ACT_NONE = 0, ACT_SWISH = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_SWISH_D = 4 };
 
 // ---- the deferred parameter-gradient queue (nnhipWeightGradDefer) ------------------------------------------------------------
@@ -115,6 +117,40 @@ static int check_linear(const char* fn, const void* X, const void* W, int64_t ro
     return 0;
 }
 
+// ---- the weight-streaming forward for 1..8 rows (linear_gemv.hip; ABI 214) ------------------------------------------------------
+// Process-wide and off by default: the kernel adds in another order than the GEMM, so logits move in their last bits and a seeded
+// sampler may pick other tokens.  While it is on, nnhipLinearModuleForward[Ex] hands the shapes linear_gemv_wanted() names to the
+// kernel, in either GEMM mode.  Nothing else reads the switch.
+static int g_linear_gemv = 0;
+// The dispatch rule, a function of (rows, in, out) only (DESIGN.md section 5.12 has the numbers behind it).
+static bool linear_gemv_wanted(int64_t rows, int64_t in, int64_t out) {
+    return rows >= 1 && rows <= NNHIP_LINEAR_GEMV_MAX_ROWS && in >= 1 && out >= 1;
+}
+
+extern "C" int nnhipSetLinearGemv(int enable) {
+    NNHIP_CHECK_ARG(enable == 0 || enable == 1, NNHIP_EINVAL, "nnhipSetLinearGemv: 0 = off (default), 1 = Linear forwards of 1..8 rows stream the weights");
+    g_linear_gemv = enable;
+    return 0;
+}
+extern "C" int nnhipGetLinearGemv(void) { return g_linear_gemv; }
+
+extern "C" int nnhipLinearGemvForward(const float* X, const float* W, const float* b, const float* addend, float* O, int64_t rows,
+                                      int64_t in_features, int64_t out_features, nnhipStream_t stream) {
+    NNHIP_CHECK_ARG(rows >= 0 && in_features >= 0 && out_features >= 0, NNHIP_EINVAL, "nnhipLinearGemvForward: negative size");
+    NNHIP_CHECK_ARG(rows <= NNHIP_LINEAR_GEMV_MAX_ROWS, NNHIP_EINVAL, "nnhipLinearGemvForward: rows must be <= %d (NNHIP_LINEAR_GEMV_MAX_ROWS)",
+                    NNHIP_LINEAR_GEMV_MAX_ROWS);
+    NNHIP_CHECK_ARG(aligned4(X) && aligned4(W) && aligned4(b) && aligned4(addend) && aligned4(O), NNHIP_EALIGN,
+                    "nnhipLinearGemvForward: misaligned pointer");
+    if (rows == 0 || out_features == 0) return 0;
+    NNHIP_CHECK_ARG(O != nullptr, NNHIP_EINVAL, "nnhipLinearGemvForward: null output");
+    // nothing to stream: O = b + addend, written by the path nnhipLinearModuleForwardEx takes for these arguments
+    if (in_features == 0)
+        return gemm_f32_add(X, W, O, b, addend, rows, out_features, in_features, in_features, in_features, out_features, true, true,
+                            (hipStream_t)stream);
+    NNHIP_CHECK_ARG(X && W, NNHIP_EINVAL, "nnhipLinearGemvForward: null X/W");
+    return linear_gemv(X, W, b, addend, O, rows, in_features, out_features, (hipStream_t)stream);
+}
+
 extern "C" int nnhipLinearModuleForward(const float* X, const float* W, const float* b, float* O,
                                         int64_t rows, int64_t in_features, int64_t out_features,
                                         nnhipStream_t stream) {
@@ -128,6 +164,8 @@ extern "C" int nnhipLinearModuleForwardEx(const float* X, const float* W, const 
     if (rows == 0) return 0;
     NNHIP_CHECK_ARG(O != nullptr, NNHIP_EINVAL, "nnhipLinearModuleForward: null output");
     NNHIP_CHECK_ARG(aligned4(addend), NNHIP_EALIGN, "nnhipLinearModuleForward: misaligned addend");
+    if (g_linear_gemv && linear_gemv_wanted(rows, in_features, out_features) && aligned4(b) && aligned4(O))
+        return linear_gemv(X, W, b, addend, O, rows, in_features, out_features, (hipStream_t)stream);
     return gemm_f32_add(X, W, O, b, addend, rows, out_features, in_features, in_features, in_features,
                         out_features, true, true, (hipStream_t)stream);
 }

@@ -107,6 +107,36 @@ def sample_top_k(logits, top_k, temperature=1.0, seed=0, seed_dev=None, out=None
     return (out, u) if return_u else out
 
 
+def set_linear_gemv(enable: bool) -> None:
+    """The process-wide switch nnhipSetLinearGemv: while it is on, a Linear forward of 1..8 rows (nnhipLinearModuleForward[Ex], which
+    is every nn.Linear / HIPLinear forward, `residual=` included) streams its weights through the GEMV kernel instead of the tiled
+    GEMM.  Off by default: the kernel adds in another order, so results move in their last bits."""
+    from ._lib import call_hip_function
+    call_hip_function("nnhipSetLinearGemv", 1 if enable else 0)
+
+
+def get_linear_gemv() -> bool:
+    from ._lib import call_hip_function
+    return bool(call_hip_function("nnhipGetLinearGemv"))
+
+
+class linear_gemv:
+    """`with neunet_hip.linear_gemv():` -- the switch of set_linear_gemv for the duration of a block; the value it had before comes
+    back on exit, exceptions included."""
+
+    def __init__(self, enable=True):
+        self.enable = bool(enable)
+
+    def __enter__(self):
+        self.previous = get_linear_gemv()
+        set_linear_gemv(self.enable)
+        return self
+
+    def __exit__(self, *exc):
+        set_linear_gemv(self.previous)
+        return False
+
+
 def save(obj, path):
     """neunet.save = pickle (neunet/__init__.py:26-29)."""
     import pickle

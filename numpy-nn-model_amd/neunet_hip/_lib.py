@@ -83,6 +83,9 @@ _SIGNATURES = {
     "nnhipLinearActivationForward": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int32, c_float, c_void_p]),
     "nnhipLinearModuleForwardEx": (ctypes.c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipLinearModuleBackwardEx": (ctypes.c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipLinearGemvForward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipSetLinearGemv": (ctypes.c_int, [ctypes.c_int]),
+    "nnhipGetLinearGemv": (ctypes.c_int, []),
     "nnhipLinearSwishForward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_float, ctypes.c_int, c_void_p]),
     "nnhipLinearSwishBackward": (ctypes.c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_float, ctypes.c_int, c_void_p]),
     "nnhipGemmF32": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_int, ctypes.c_int,
@@ -186,7 +189,7 @@ _SIGNATURES = {
     "nnhipBroadcastF32": (ctypes.c_int, [c_void_p, P, c_int64, ctypes.c_int, c_void_p]),
 }
 _NO_STATUS = {"nnhipVersion", "nnhipLinearReLULinearBackwardFits", "nnhipBatchNorm2dLinearSigmoidMSEFits", "nnhipConv2dLeakyMaxPoolStatsBlocks", "nnhipGetLastErrorString", "nnhipCreateFusedOptimizer", "nnhipGetGemmMode", "nnhipGetGemmLockstep", "nnhipConv2dWeightGradPooledOk", "nnhipConv2dLeakyMaxPoolForwardOk", "nnhipGemmLaunchCount",
-              "nnhipWeightGradPending"}
+              "nnhipWeightGradPending", "nnhipGetLinearGemv"}
 
 _dll = None
 _funcs: dict = {}

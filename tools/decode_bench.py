@@ -18,6 +18,11 @@
               inside the captured step).
   sampler     one nnhipSampleTopK call (top_k 40) beside one nnhipArgmaxF32 call on the same [B, 50257] logits, B 1 and 32: both
               read every logit once.
+  linear      the five Linear shapes of GPT-2 small (768 -> 2304, 768 -> 768, 768 -> 3072, 3072 -> 768, 768 -> 50257) at 1, 2, 4 and 8
+              rows: nnhipLinearModuleForwardEx with the GEMV switch off (the tiled GEMM, its split-K reduce included) and
+              nnhipLinearGemvForward, alternating in one process over a ring of weight copies larger than the Infinity Cache, as a
+              decode step meets its weights; the algorithmic bytes 4 (in out + rows (in + out)) over each time, and the read-only
+              stream at the same footprint.  The generate section then runs graph mode at B 1 and 8 with --linear gemm and gemv.
   families    (a rocprofv3 run of its own, then a summary) device time per kernel family of B = 1 graph-replayed decode steps:
               Linear, attention, norms / activations / embedding, the gaps between kernels, and Linear's distance from streaming
               every weight once.
@@ -137,6 +142,60 @@ def bench_rows(reps):
     return res
 
 
+LINEAR_SHAPES = ((768, 2304), (768, 768), (768, 3072), (3072, 768), (768, 50257))       # (in, out): c_attn, attn c_proj, c_fc, mlp c_proj, lm_head
+LINEAR_ROWS = (1, 2, 4, 8)
+RING_BYTES = 600 << 20               # weight copies cycled per shape: more than the 256 MiB Infinity Cache, so every call reads HBM
+
+
+def bench_linear(reps):
+    """Per (shape, rows): median device time of the tiled-GEMM path (switch off) and of the GEMV kernel, alternating call by call."""
+    import torch
+    import neunet_hip
+    from neunet_hip import _lib
+    st = _lib.get_current_stream_ptr
+    call = _lib.call_hip_function
+    res = []
+    neunet_hip.set_linear_gemv(False)
+    for n_in, n_out in LINEAR_SHAPES:
+        copies = max(2, min(256, -(-RING_BYTES // (4 * n_in * n_out))))
+        Ws = [torch.randn((n_out, n_in), device="cuda") * 0.02 for _ in range(copies)]
+        b = torch.randn((n_out,), device="cuda")
+        n = n_in * n_out
+        it = {"i": 0}
+
+        def rsum():
+            torch.sum(Ws[it["i"] % copies])
+            it["i"] += 1
+        us_read = event_median(rsum, reps, warm=min(copies, 12))
+        for rows in LINEAR_ROWS:
+            X = torch.randn((rows, n_in), device="cuda")
+            add = torch.randn((rows, n_out), device="cuda")
+            O = torch.empty((rows, n_out), device="cuda")
+            fns = {"gemm": lambda: call("nnhipLinearModuleForwardEx", X, Ws[it["i"] % copies], b, add, O, rows, n_in, n_out, st()),
+                   "gemv": lambda: call("nnhipLinearGemvForward", X, Ws[it["i"] % copies], b, add, O, rows, n_in, n_out, st())}
+            ts = {"gemm": [], "gemv": []}
+            for k in range(2 * (reps + 6)):                                 # alternate: gemm, gemv, gemm, ... (the first 6 of each: warm-up)
+                name = ("gemm", "gemv")[k & 1]
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fns[name]()
+                e1.record()
+                e1.synchronize()
+                it["i"] += 1
+                if k >= 12:
+                    ts[name].append(e0.elapsed_time(e1) * 1e3)
+            us = {k: statistics.median(v) for k, v in ts.items()}
+            nbytes = 4 * (n + rows * (n_in + n_out))
+            res.append({"in": n_in, "out": n_out, "rows": rows, "bytes": nbytes, "weight_copies_cycled": copies,
+                        "gemm_us": round(us["gemm"], 2), "gemv_us": round(us["gemv"], 2),
+                        "gemm_GBps": round(nbytes / us["gemm"] / 1e3, 1), "gemv_GBps": round(nbytes / us["gemv"] / 1e3, 1),
+                        "gemv_over_gemm": round(us["gemv"] / us["gemm"], 3),
+                        "read_stream_us": round(us_read, 2), "read_stream_GBps": round(4 * n / us_read / 1e3, 1),
+                        "gemv_over_read_stream": round(us["gemv"] / (us_read * nbytes / (4 * n)), 3)})
+        del Ws
+    return res
+
+
 def build_model(seed=0):
     import numpy as np
     import gpt2_infer as G
@@ -192,6 +251,22 @@ def bench_generate(stream_GBps):
                                         "tokens_per_s_token_loop": round(B * 127 / stats["decode_s"], 1),
                                         "host_syncs_between_tokens": stats["host_syncs_between_tokens"],
                                         "kernel_nodes": stats.get("kernel_nodes"), "graph_nodes": stats.get("graph_nodes")})
+    # graph mode, greedy, at the batch sizes the GEMV kernel takes (1..8 rows per step): the tiled GEMM beside --linear gemv
+    res["linear_runs"] = []
+    for B in (1, 8):
+        ids = rng.integers(0, G.GPT2_SMALL["vocab_size"], (B, 128)).astype(np.int32)
+        toks = {}
+        for linear in ("gemm", "gemv"):
+            G.generate(model, ids, 4, mode="graph", linear=linear)
+            stats = {}
+            t0 = time.perf_counter()
+            toks[linear] = G.generate(model, ids, 128, mode="graph", stats=stats, linear=linear)
+            wall = time.perf_counter() - t0
+            res["linear_runs"].append({"B": B, "mode": "graph", "linear": linear, "wall_s": round(wall, 4),
+                                       "decode_s": round(stats["decode_s"], 4), "ms_per_step": round(stats["decode_s"] / 127 * 1e3, 4),
+                                       "tokens_per_s_token_loop": round(B * 127 / stats["decode_s"], 1),
+                                       "kernel_nodes": stats.get("kernel_nodes"), "graph_nodes": stats.get("graph_nodes")})
+        res[f"gemv_same_tokens_as_gemm_B{B}"] = bool(np.array_equal(toks["gemm"], toks["gemv"]))      # reported, not required
     return res
 
 
@@ -215,7 +290,7 @@ def family_of(name):
     n = name.replace("void ", "").replace("nnhip::", "")
     if n.startswith("attn_decode"):
         return "attention"
-    if n.startswith(("gemm_", "sg_", "splitk_", "colsum_")):           # every Linear: the GEMM kernels and their reduces / bias sums
+    if n.startswith(("gemm_", "sg_", "splitk_", "colsum_", "linear_gemv_")):   # every Linear: the GEMM kernels, their reduces / bias sums, the GEMV
         return "linear"
     if n.startswith(("layernorm_", "map1_kernel", "map2_kernel", "embedding_", "argmax_", "sample_", "at::native")):
         return "norm_act_embed"                                        # (at::native: torch's cache_len += 1)
@@ -276,8 +351,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--skip-generate", action="store_true")
-    ap.add_argument("--only", default=None, choices=["sampler", "generate"], help="only this section (generate: with the read-stream rate "
-                    "given by --stream-GBps instead of the attention section's measurement)")
+    ap.add_argument("--only", default=None, choices=["sampler", "generate", "linear"], help="only this section (generate: with the read-stream "
+                    "rate given by --stream-GBps instead of the attention section's measurement)")
     ap.add_argument("--stream-GBps", type=float, default=0.0)
     ap.add_argument("--families-run", type=int, default=0, metavar="STEPS", help="only the workload of the per-family profile")
     ap.add_argument("--families-summary", nargs=3, metavar=("KERNEL_STATS_CSV", "BENCH_JSON", "STEPS"),
@@ -292,6 +367,9 @@ def main():
     if a.families_run:
         families_run(a.families_run)
         return
+    if a.only == "linear":
+        print(json.dumps({"linear": bench_linear(a.reps)}))
+        return
     if a.only:
         res = {"sampler": bench_sampler(a.reps)}
         if a.only == "generate":
@@ -301,7 +379,7 @@ def main():
         print(json.dumps(res))
         return
     res = {"H": H, "dh": DH, "Tmax": TMAX, "layers_cycled": LAYERS, "attention": bench_attention(a.reps), "rows": bench_rows(a.reps),
-           "sampler": bench_sampler(a.reps)}
+           "sampler": bench_sampler(a.reps), "linear": bench_linear(a.reps)}
     if not a.skip_generate:
         big = max(r["read_stream_GBps"] for r in res["attention"])      # the read-only stream at the largest footprint
         res["generate"] = bench_generate(big)
