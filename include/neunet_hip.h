@@ -28,7 +28,7 @@ typedef void* nnhipStream_t; /* hipStream_t */
 
 #define NNHIP_OK 0
 #define NNHIP_EINVAL (-1)   /* bad argument (null pointer, negative size, bad enum) */
-#define NNHIP_EALIGN (-2)   /* pointer not 4-byte aligned */
+#define NNHIP_EALIGN (-2)   /* pointer not aligned as the entry requires (4 bytes unless the entry says otherwise) */
 #define NNHIP_ENOMEM (-3)   /* workspace allocation failed */
 #define NNHIP_EDEVICE (-5)  /* a kernel of an EARLIER launch found the device state broken and raised the library's device error
                              * word; sticky until nnhipClearDeviceError() (-4 is NNHIP_ECOMM, below) */
@@ -283,7 +283,12 @@ int nnhipMaskedSoftmaxBackwardEx(float* dX, const float* dY, const float* Y, con
  * are [B,T,*] with row stride ld_qkv floats (0 = H*head_dim; 3*H*head_dim when they are the three column blocks of one fused
  * q|k|v projection buffer).  LSE [B,H,Tq,2] = (row max, log2 row sum) of each masked score row in log2 units, saved by the
  * forward and consumed by the backward; the pair is kept apart because a fully-masked row has max = -1e9*log2(e),
- * where fp32 cannot hold max + log(sum). */
+ * where fp32 cannot hold max + log(sum).
+ * Status (all checked on the host before any launch; nothing is written when a call is refused): a NULL operand or output, Tk == 0 with
+ * Tq > 0 (forward), a head_dim other than 32 / 64 / 128, ld_qkv that is neither 0 nor a multiple of 4 that is >= H*head_dim, mask_bits
+ * without mask_bitsT, dropout_p outside [0, 1): NNHIP_EINVAL.  Q, K, V, O, dO, dQ, dK, dV not 16-byte aligned, or LSE not 8-byte aligned
+ * (the kernels store and load a row's pair as one float2): NNHIP_EALIGN -- since ABI 215 from the forward too, which used to answer
+ * NNHIP_EINVAL for a misaligned O and did not check LSE.  B == 0 or Tq == 0 (backward: or Tk == 0): returns 0, launches nothing. */
 int nnhipAttentionForward(const float* Q, const float* K, const float* V, const int32_t* key_valid, float* O,
                           float* LSE, int64_t B, int64_t H, int64_t Tq, int64_t Tk, int64_t head_dim, int64_t ld_qkv,
                           float scale, int causal, nnhipStream_t stream);

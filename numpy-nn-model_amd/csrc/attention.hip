@@ -1009,7 +1009,9 @@ extern "C" int nnhipAttentionForwardEx(const float* Q, const float* K, const flo
     if (int rc = attn_check("nnhipAttentionForward", Q, K, V, B, H, Tq, Tk, head_dim, ld_qkv)) return rc;
     if (B == 0 || Tq == 0) return 0;
     NNHIP_CHECK_ARG(Tk > 0, NNHIP_EINVAL, "nnhipAttentionForward: Tk must be > 0");
-    NNHIP_CHECK_ARG(O && LSE && aligned16(O), NNHIP_EINVAL, "nnhipAttentionForward: null / misaligned output");
+    NNHIP_CHECK_ARG(O && LSE, NNHIP_EINVAL, "nnhipAttentionForward: null output");
+    NNHIP_CHECK_ARG(aligned16(O) && aligned8(LSE), NNHIP_EALIGN,
+                    "nnhipAttentionForward: O must be 16-byte aligned and LSE 8-byte aligned (it is stored as float2)");
     AttnParams p;
     if (int rc = fill_extra("nnhipAttentionForward", p.x, opts, key_valid, causal)) return rc;
     p.Q = Q; p.K = K; p.V = V; p.O = O; p.LSE = LSE; p.key_valid = key_valid;
@@ -1037,8 +1039,8 @@ extern "C" int nnhipAttentionBackwardEx(const float* Q, const float* K, const fl
     if (int rc = attn_check("nnhipAttentionBackward", Q, K, V, B, H, Tq, Tk, head_dim, ld_qkv)) return rc;
     if (B == 0 || Tq == 0 || Tk == 0) return 0;
     NNHIP_CHECK_ARG(O && dO && LSE && dQ && dK && dV, NNHIP_EINVAL, "nnhipAttentionBackward: null pointer");
-    NNHIP_CHECK_ARG(aligned16(dO) && aligned16(O) && aligned16(dQ) && aligned16(dK) && aligned16(dV), NNHIP_EALIGN,
-                    "nnhipAttentionBackward: O/dO/dQ/dK/dV must be 16-byte aligned");
+    NNHIP_CHECK_ARG(aligned16(dO) && aligned16(O) && aligned16(dQ) && aligned16(dK) && aligned16(dV) && aligned8(LSE), NNHIP_EALIGN,
+                    "nnhipAttentionBackward: O/dO/dQ/dK/dV must be 16-byte aligned and LSE 8-byte aligned (it is read as float2)");
     hipStream_t st = (hipStream_t)s;
     float* dsum = static_cast<float*>(workspace((size_t)B * H * Tq * sizeof(float)));
     NNHIP_CHECK_ARG(dsum != nullptr, NNHIP_ENOMEM, "nnhipAttentionBackward: workspace allocation failed");

@@ -179,7 +179,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 214; }
+extern "C" int nnhipVersion(void) { return 215; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 

@@ -142,3 +142,51 @@ def test_comm_unique_id_needs_no_gpu(lib):
         h = ctypes.c_void_p()
         _lib.call_hip_function("nnhipCommInitRank", ctypes.byref(h), buf.raw, 3, 2)
     assert _lib.call_hip_function("nnhipCommDestroy", None) == 0
+
+
+def test_attention_status_codes_need_no_device(lib):
+    """The fused attention entries' argument checks (attn_check, fill_extra and the head of the two entries in csrc/attention.hip) all
+    precede the first device call: the pointers here are never dereferenced.  ABI 215: the forward answers NNHIP_EALIGN (it said
+    NNHIP_EINVAL) for an O that is not 16-byte aligned, and both entries require LSE 8-byte aligned (the kernels store and load a
+    row's (max, log2 sum) as one float2).  (The backward looks at its options after it has asked for its workspace, a device call:
+    its two option refusals need a GPU and are not checked here.)"""
+    from neunet_hip import _lib
+    EINVAL, EALIGN = -1, -2
+    assert _lib.load_hip_function("nnhipVersion")() >= 215
+    fwd, bwd = _lib.load_hip_function("nnhipAttentionForwardEx"), _lib.load_hip_function("nnhipAttentionBackwardEx")
+    D = 0x1000                                                  # non-null, 16-byte aligned, never dereferenced
+    base = dict(B=2, H=2, Tq=8, Tk=8, dh=64, ld=0, opts=None)
+
+    def call(entry, names, off, kw):
+        s = dict(base, **kw)
+        opts = None if s["opts"] is None else ctypes.byref(s["opts"])
+        rc = entry(*[D + off.get(n, 0) for n in names], s["B"], s["H"], s["Tq"], s["Tk"], s["dh"], s["ld"], 0.1, 1, opts, None)
+        assert rc == 0 or "nnhipAttention" in _lib.last_error()
+        return rc
+
+    def forward(off={}, **kw):
+        return call(fwd, ("Q", "K", "V", "kv", "O", "LSE"), off, kw)
+
+    def backward(off={}, **kw):
+        return call(bwd, ("Q", "K", "V", "kv", "O", "dO", "LSE", "dQ", "dK", "dV"), off, kw)
+
+    for entry, names in ((forward, ("Q", "K", "V", "O")), (backward, ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV"))):
+        for n in names:
+            for by in (4, 8):
+                assert entry({n: by}) == EALIGN, (entry.__name__, n, by)
+                assert "16-byte aligned" in _lib.last_error()
+            assert entry({n: -D}) == EINVAL and "null" in _lib.last_error(), (entry.__name__, n)
+        assert entry({"LSE": 4}) == EALIGN and "LSE 8-byte aligned" in _lib.last_error()
+        assert entry({"LSE": -D}) == EINVAL and "null" in _lib.last_error()      # a NULL LSE stays NNHIP_EINVAL
+        assert entry(dh=48) == EINVAL and "head_dim" in _lib.last_error()
+        assert entry(ld=2 * 64 - 4) == EINVAL and "ld_qkv" in _lib.last_error()
+        assert entry(ld=2 * 64 + 2) == EINVAL and "ld_qkv" in _lib.last_error()
+        assert entry(H=0) == EINVAL and entry(B=-1) == EINVAL and entry(Tq=1 << 24) == EINVAL
+        assert entry(B=0) == 0 and entry(Tq=0) == 0                              # nothing to do: no launch, whatever the pointers are
+    assert forward(Tk=0) == EINVAL and "Tk" in _lib.last_error()
+    assert backward(Tk=0) == 0
+    half, p_one = _lib.AttentionOptions(), _lib.AttentionOptions()
+    half.mask_bits = D
+    p_one.dropout_p = 1.0
+    assert forward({"LSE": 8}, opts=half) == EINVAL and "mask_bitsT" in _lib.last_error()     # (LSE + 8 bytes is aligned)
+    assert forward(opts=p_one) == EINVAL and "dropout_p" in _lib.last_error()
