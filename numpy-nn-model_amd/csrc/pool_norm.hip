@@ -359,8 +359,13 @@ __global__ __launch_bounds__(1024) void bn_bwd_fused_kernel(const float* __restr
     for (int e = 0; e < BN_NE; ++e)
         if (off[e] >= 0) dc_[off[e]] = wc * gv[e] * iv + dstd * 2.0f * xc[e] * invN + t2 * iv * (-1.0f) * invN;
 }
-// (also guarantees that every offset fits an int: B * HW <= 16384 elements per channel, C * that < 2^31 for C < 131072)
-static inline bool bn_fits_fused(int64_t B, int64_t C, int64_t HW) { return ceil_div(B, 16) * ceil_div(HW, 64) <= BN_NE && C < 131072; }
+// Also guarantees that every offset fits an int, as an ELEMENT offset (the stores: B * HW <= 16384 elements per channel, C * that
+// < 2^31 for C < 131072) and as the BYTE offset bn_ld() hands the buffer load (off * 4 in int: B * C * HW <= 2^29 floats keeps it below
+// 2^31; without that bound a tensor beyond 2^30 floats read its last images from a wrapped, lower address -- silently).  Larger
+// tensors take the two-launch kernels, which index in 64 bits.
+static inline bool bn_fits_fused(int64_t B, int64_t C, int64_t HW) {
+    return ceil_div(B, 16) * ceil_div(HW, 64) <= BN_NE && C < 131072 && B * C * HW <= ((int64_t)1 << 29);
+}
 
 // ---- MSELoss (neunet/nn/losses.py:9-22): loss = sum((p - t)^2) / N ; dp = 2 (p - t) / N -------------------------
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ p, const float* __restrict__ t,
