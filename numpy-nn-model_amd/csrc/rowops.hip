@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "common.h"
@@ -104,10 +105,12 @@ __device__ __forceinline__ float row_max(float v, float* red) {
     else return block_max<TPR / 64>(v, red);
 }
 
-// block = max(TPR,256) threads; rows per block = blockDim/TPR
+// Launch geometry of every row kernel: block = max(TPR,256) threads; rows per block = blockDim/TPR
+constexpr int row_block(int tpr) { return tpr >= 256 ? tpr : 256; }
+constexpr int row_rpb(int tpr) { return tpr >= 256 ? 1 : 256 / tpr; }
 #define ROW_PROLOGUE(TPR)                                                     \
     __shared__ float red[16];                                                 \
-    constexpr int RPB = (TPR >= 256) ? 1 : 256 / TPR;                         \
+    constexpr int RPB = row_rpb(TPR);                                         \
     const int t = RPB > 1 ? threadIdx.x % TPR : threadIdx.x;                  \
     const int64_t row = (int64_t)blockIdx.x * RPB + (RPB > 1 ? threadIdx.x / TPR : 0); /* uniform when a block owns one row */ \
     if (TPR == 64 && row >= rows) return; /* wave-uniform; no block barriers in the TPR=64 path */ \
@@ -117,7 +120,7 @@ __device__ __forceinline__ float row_max(float v, float* red) {
 // Softmax   (neunet/nn/activations.py:448-459 fwd, 437-446 bwd)
 // =================================================================================================
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_fwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void softmax_fwd_rows(
     float* __restrict__ out, const float* __restrict__ in, int64_t rows, int64_t cols, int nt) {
     ROW_PROLOGUE(TPR)
     RowTile<TPR, NV, VEC> r;
@@ -140,7 +143,7 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_fwd_rows(
 }
 
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_bwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void softmax_bwd_rows(
     float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y, int64_t rows,
     int64_t cols, int nt) {
     ROW_PROLOGUE(TPR)
@@ -161,7 +164,7 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_bwd_rows(
 // Row r <-> (b, h, i); column j is masked when key j of batch b is padding (key_valid[b,j] == 0) or, if
 // `causal`, j > i + (cols - Tq).  Masked scores are REPLACED by -1e9 (not -inf), exactly like the reference.
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_masked_fwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void softmax_masked_fwd_rows(
     float* out, const float* in, const int32_t* __restrict__ key_valid,  // out may alias in
     int64_t rows, int64_t cols, int64_t HTq, int64_t Tq, float scale, int causal, const int32_t* __restrict__ dense) {
     ROW_PROLOGUE(TPR)
@@ -198,7 +201,7 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_masked_fwd_r
 
 // d(raw scores) = where(mask, 0, (dy - sum(dy*y)) * y) * scale
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void softmax_masked_bwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void softmax_masked_bwd_rows(
     float* dx, const float* dy, const float* __restrict__ y,  // dx may alias dy
     const int32_t* __restrict__ key_valid, int64_t rows, int64_t cols, int64_t HTq, int64_t Tq,
     float scale, int causal, const int32_t* __restrict__ dense) {
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_looped(float* __restrict__ dx
 // RMSNorm   (neunet/nn/layers/rmsnorm.py:84-94 fwd, 43-59 bwd)
 // =================================================================================================
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void rmsnorm_fwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void rmsnorm_fwd_rows(
     const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ b,
     float* __restrict__ Y, float* __restrict__ Xstd, float* __restrict__ Xnorm, int64_t rows,
     int64_t cols, float eps, int nt) {
@@ -520,31 +523,69 @@ static void colsum_queue(const float* part, float* out, int64_t prow, int64_t co
     g_csq[g_csq_n++] = ColsumJob{part, out, prow, cols};
 }
 
-// Backward: block b walks rows b*RPB+rslot + k*gridDim.x*RPB, one row per iteration with the next row's loads already
+// ---- the persistent norm backward, shared by RMSNorm and LayerNorm ---------------------------------------------------
+// Block b walks rows b*RPB+rslot + k*gridDim.x*RPB, one row per iteration with the next row's loads already
 // in flight, keeps per-thread column
-// partials of dw = sum dy*x/std and db = sum dy in registers (a thread always owns the same columns),
+// partials of dw = sum dy*xhat and db = sum dy in registers (a thread always owns the same columns),
 // and writes them once at the end to part[b][cols] (wave-per-row blocks first add their 4 waves' partials in LDS).
 // dw/db are finished by ONE more launch for both (colsum_tall_kernel; round 1 used two two-stage column sums = up to
 // four launches).  Finishing them inside this launch -- arrival ticket after an agent-scope release, the last blocks
 // to arrive column-sum the partials -- was built and measured in round 2: 107 us instead of 81 at 8192x4096, 39
 // instead of 23 at 16384x512 (every block's release fence writes back its XCD's whole L2, which is full of dirty dX
 // lines, and the finishers start from cold caches); a kernel boundary costs ~1.7 us (MI355X_MICROARCH.md).
-// dx needs one row reduction: S = sum(w dy x / std).
-template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void rmsnorm_bwd_rows(
-    const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
-    const float* __restrict__ Xstd, float* __restrict__ dX, float* __restrict__ part_dw, float* __restrict__ part_db,
-    int64_t rows, int64_t cols, const float* __restrict__ dXadd, int nt) {
-    constexpr int RPB = (TPR >= 256) ? 1 : 256 / TPR;
+//
+// A norm is a policy struct that holds the saved row statistics and supplies only what differs:
+//   kOptional          w, part_dw and part_db may each be null (both partials null: nothing is published)
+//   stats(r)           the row's saved statistics
+//   accumulate(...)    one element: dw/db partials += it, g <- w * dy, the row sums s1 (s2) += it
+//   reduce<NW>(...)    the row sums over the row's threads, times 1/cols
+//   dx(...)            one element of dX
+//   add(v, a)          dx + the dX addend
+//   xhat(x, r)         the normalised value of x in row r, as the wide-row column pass (norm_bwd_dwdb_cols) takes it
+
+// 4 waves = 4 row slots with the same column ownership: add them in LDS (slots 1..3 deposit, slot 0 sums in
+// slot order), so a block publishes ONE partial row (4x less to re-read in the finish).
+// xch: 256 float4 = 1024 floats >= 3 slots x EPP x 64 per pass
+template <int NV, bool VEC>
+__device__ __forceinline__ void fold_row_slots(RowTile<64, NV, VEC>& acc, float* xch, int rslot, int t) {
+    constexpr int NE = NV * 4;
+    constexpr int EPP = (1024 / (3 * 64)) < NE ? (1024 / (3 * 64)) : NE;   // elements per pass (5 of <= 16)
+#pragma unroll
+    for (int e0 = 0; e0 < NE; e0 += EPP) {
+        __syncthreads();
+        if (rslot > 0) {
+#pragma unroll
+            for (int e = 0; e < EPP; ++e)
+                if (e0 + e < NE) xch[((rslot - 1) * EPP + e) * 64 + t] = acc.x[e0 + e];
+        }
+        __syncthreads();
+        if (rslot == 0) {
+#pragma unroll
+            for (int e = 0; e < EPP; ++e)
+                if (e0 + e < NE)
+                    acc.x[e0 + e] += (xch[(0 * EPP + e) * 64 + t] + xch[(1 * EPP + e) * 64 + t]) + xch[(2 * EPP + e) * 64 + t];
+        }
+    }
+}
+
+template <class Norm, int TPR, int NV, bool VEC>
+__device__ __forceinline__ void norm_bwd_rows(
+    const Norm norm, const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
+    float* __restrict__ dX, float* __restrict__ part_dw, float* __restrict__ part_db, int64_t rows, int64_t cols,
+    const float* __restrict__ dXadd, int nt) {
+    constexpr int RPB = row_rpb(TPR);
     constexpr int NW = TPR / 64;
     __shared__ float red[32];
     __shared__ float4 fin_lds[RPB > 1 ? 256 : 1];
     const int t = threadIdx.x % TPR;
     const int rslot = RPB > 1 ? threadIdx.x / TPR : 0;   // a compile-time 0 keeps the row pointers in scalar registers
     RowTile<TPR, NV, VEC> wt, adw, adb;
-    wt.load(w, cols, t, 0.f);
+    if (!Norm::kOptional || w) wt.load(w, cols, t, 0.f);
 #pragma unroll
-    for (int e = 0; e < wt.NE; ++e) adw.x[e] = adb.x[e] = 0.f;
+    for (int e = 0; e < wt.NE; ++e) {
+        adw.x[e] = adb.x[e] = 0.f;
+        if (Norm::kOptional && !w) wt.x[e] = 1.f;
+    }
     const float invN = 1.0f / (float)cols;
     const int64_t step = (int64_t)gridDim.x * RPB;
     // when TPR >= 256 every thread of the block runs the same trip count (block barriers inside)
@@ -572,24 +613,17 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void rmsnorm_bwd_rows(
             x0.load(X + r0 * cols, cols, t, 0.f, nt);
             g0.load(dY + r0 * cols, cols, t, 0.f, nt);
         }
-        const float sd0 = Xstd[r0];
-        const float i0 = 1.0f / sd0;
-        float s0 = 0.f;
+        const auto st = norm.stats(r0);
+        float s1 = 0.f, s2 = 0.f;             // the row sums dx needs (RMSNorm: one)
 #pragma unroll
-        for (int e = 0; e < x0.NE; ++e) {
-            adb.x[e] += g0.x[e];
-            adw.x[e] += g0.x[e] * (x0.x[e] * i0);
-            g0.x[e] *= wt.x[e];  // dX_hat = w * dy
-            s0 += g0.x[e] * x0.x[e] * i0;
-        }
-        s0 = block_sum<NW>(s0, red) * invN;
-        const float q0 = i0 * i0;
+        for (int e = 0; e < x0.NE; ++e) norm.accumulate(st, x0.x[e], g0.x[e], wt.x[e], adw.x[e], adb.x[e], s1, s2);
+        Norm::template reduce<NW>(s1, s2, invN, red);
 #pragma unroll
-        for (int e = 0; e < x0.NE; ++e) g0.x[e] = (g0.x[e] * sd0 - x0.x[e] * s0) * q0;
-        if (dXadd) {   // dX = rmsnorm gradient + an already accumulated gradient of X (x0 is dead: reuse it)
+        for (int e = 0; e < x0.NE; ++e) g0.x[e] = norm.dx(st, g0.x[e], x0.x[e], s1, s2);
+        if (dXadd) {   // dX = the norm's gradient + an already accumulated gradient of X (x0 is dead: reuse it)
             x0.load(dXadd + r0 * cols, cols, t, 0.f);
 #pragma unroll
-            for (int e = 0; e < x0.NE; ++e) g0.x[e] += x0.x[e];
+            for (int e = 0; e < x0.NE; ++e) g0.x[e] = Norm::add(g0.x[e], x0.x[e]);
         }
         g0.store(dX + r0 * cols, cols, t);
         if constexpr (PRE) {
@@ -598,39 +632,75 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void rmsnorm_bwd_rows(
         }
     }
     // ---- this block's column partials -> part[blockIdx.x][cols] ---------------------------------------------------
+    const bool has_dw = !Norm::kOptional || part_dw;
+    if (!has_dw && !part_db) return;       // elementwise_affine=False (uniform for the whole grid)
     if constexpr (RPB > 1) {
-        // 4 waves = 4 row slots with the same column ownership: add them in LDS (slots 1..3 deposit, slot 0 sums in
-        // slot order), so a block publishes ONE partial row (4x less to re-read in the finish)
-        float* xch = reinterpret_cast<float*>(fin_lds);      // 256 float4 = 1024 floats >= 3 slots x NE x 64 / pass
-        constexpr int NE = NV * 4;
-        constexpr int EPP = (1024 / (3 * 64)) < NE ? (1024 / (3 * 64)) : NE;   // elements per pass (5 of <= 16)
-        auto fold = [&](RowTile<TPR, NV, VEC>& acc) {
-#pragma unroll
-            for (int e0 = 0; e0 < NE; e0 += EPP) {
-                __syncthreads();
-                if (rslot > 0) {
-#pragma unroll
-                    for (int e = 0; e < EPP; ++e)
-                        if (e0 + e < NE) xch[((rslot - 1) * EPP + e) * 64 + t] = acc.x[e0 + e];
-                }
-                __syncthreads();
-                if (rslot == 0) {
-#pragma unroll
-                    for (int e = 0; e < EPP; ++e)
-                        if (e0 + e < NE)
-                            acc.x[e0 + e] += (xch[(0 * EPP + e) * 64 + t] + xch[(1 * EPP + e) * 64 + t]) + xch[(2 * EPP + e) * 64 + t];
-                }
-            }
-        };
-        fold(adw);
-        if (part_db) fold(adb);
+        float* xch = reinterpret_cast<float*>(fin_lds);
+        if (has_dw) fold_row_slots(adw, xch, rslot, t);
+        if (part_db) fold_row_slots(adb, xch, rslot, t);
         __syncthreads();
     }
     if (rslot == 0) {
-        adw.store(part_dw + (int64_t)blockIdx.x * cols, cols, t);
+        if (has_dw) adw.store(part_dw + (int64_t)blockIdx.x * cols, cols, t);
         if (part_db) adb.store(part_db + (int64_t)blockIdx.x * cols, cols, t);
     }
     // dw/db = column sums of the partials: colsum_tall_kernel, the next launch.
+}
+
+// dw[c] = sum_r dy[r,c] xhat[r,c], db[c] = sum_r dy[r,c] for rows wider than the register tile: thread per column
+// (coalesced across threads), rows split over gridDim.y into partials part[y][cols] that a column sum finishes.
+template <class Norm>
+__device__ __forceinline__ void norm_bwd_dwdb_cols(const Norm norm, const float* __restrict__ dY, const float* __restrict__ X,
+                                                   float* __restrict__ part_dw, float* __restrict__ part_db, int64_t rows,
+                                                   int64_t cols, int64_t rows_per_block) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t r1 = min(rows, r0 + rows_per_block);
+    float aw = 0.f, ab = 0.f;
+    for (int64_t r = r0; r < r1; ++r) {
+        const float g = dY[r * cols + c];
+        aw += g * norm.xhat(X[r * cols + c], r);
+        ab += g;
+    }
+    if (!Norm::kOptional || part_dw) part_dw[(int64_t)blockIdx.y * cols + c] = aw;
+    if (part_db) part_db[(int64_t)blockIdx.y * cols + c] = ab;
+}
+
+// RMSNorm: dx needs one row reduction, S = sum(w dy x / std).
+struct RmsNorm {
+    const float* __restrict__ Xstd;
+    static constexpr bool kOptional = false;
+    struct Row { float sd, inv; };
+    __device__ __forceinline__ Row stats(int64_t r) const {
+        const float sd = Xstd[r];
+        return {sd, 1.0f / sd};
+    }
+    // dw/db partials += this element; g <- dX_hat = w * dy; s1 += its share of S
+    __device__ __forceinline__ void accumulate(const Row& st, float& x, float& g, float w, float& adw, float& adb, float& s1,
+                                               float&) const {
+        adb += g;
+        adw += g * (x * st.inv);
+        g *= w;
+        s1 += g * x * st.inv;
+    }
+    template <int NW>
+    __device__ __forceinline__ static void reduce(float& s1, float&, float invN, float* red) {
+        s1 = block_sum<NW>(s1, red) * invN;
+    }
+    __device__ __forceinline__ float dx(const Row& st, float g, float x, float s1, float) const {
+        return (g * st.sd - x * s1) * (st.inv * st.inv);
+    }
+    __device__ __forceinline__ static float add(float v, float a) { return v + a; }   // (the compiler may contract it)
+    __device__ __forceinline__ float xhat(float x, int64_t r) const { return x / Xstd[r]; }
+};
+
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__(row_block(TPR)) void rmsnorm_bwd_rows(
+    const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
+    const float* __restrict__ Xstd, float* __restrict__ dX, float* __restrict__ part_dw, float* __restrict__ part_db,
+    int64_t rows, int64_t cols, const float* __restrict__ dXadd, int nt) {
+    norm_bwd_rows<RmsNorm, TPR, NV, VEC>(RmsNorm{Xstd}, dY, X, w, dX, part_dw, part_db, rows, cols, dXadd, nt);
 }
 
 // ---- RMSNorm for rows wider than the register tile (cols > 16384): looped, one block per row -------------------------
@@ -674,24 +744,11 @@ __global__ __launch_bounds__(1024) void rmsnorm_bwd_dx_looped(const float* __res
         dX[row * cols + i] = v;
     }
 }
-// dw[c] = sum_r dy[r,c] x[r,c] / std[r], db[c] = sum_r dy[r,c]: thread per column (coalesced across threads), rows split
-// over gridDim.y into partials part[y][cols] that a column sum finishes.
 __global__ __launch_bounds__(256) void rmsnorm_bwd_dwdb_cols(const float* __restrict__ dY, const float* __restrict__ X,
                                                              const float* __restrict__ Xstd, float* __restrict__ part_dw,
                                                              float* __restrict__ part_db, int64_t rows, int64_t cols,
                                                              int64_t rows_per_block) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= cols) return;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-    const int64_t r1 = min(rows, r0 + rows_per_block);
-    float aw = 0.f, ab = 0.f;
-    for (int64_t r = r0; r < r1; ++r) {
-        const float g = dY[r * cols + c];
-        aw += g * (X[r * cols + c] / Xstd[r]);
-        ab += g;
-    }
-    part_dw[(int64_t)blockIdx.y * cols + c] = aw;
-    if (part_db) part_db[(int64_t)blockIdx.y * cols + c] = ab;
+    norm_bwd_dwdb_cols(RmsNorm{Xstd}, dY, X, part_dw, part_db, rows, cols, rows_per_block);
 }
 
 // =================================================================================================
@@ -701,7 +758,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_dwdb_cols(const float* __rest
 // E[x^2] - mean^2 cancellation).  Saved for the backward: mean and rstd = 1/sqrt(var + eps), one float each per row -- the
 // reference keeps X_centered, a whole extra tensor.  w == nullptr: elementwise_affine=False.
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void layernorm_fwd_rows(
+__global__ __launch_bounds__(row_block(TPR)) void layernorm_fwd_rows(
     const float* __restrict__ X, const float* __restrict__ w, const float* __restrict__ b,
     float* __restrict__ Y, float* __restrict__ Mean, float* __restrict__ Rstd, int64_t rows,
     int64_t cols, float eps, int nt) {
@@ -737,112 +794,47 @@ __global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void layernorm_fwd_rows(
     r.store(Y + row * cols, cols, t);
 }
 
-// Backward, the persistent shape of rmsnorm_bwd_rows (one row per iteration with the next row's loads in flight, per-thread
-// column partials of dw = sum dy xhat and db = sum dy, one partial row per block, finished by the column-sum launch).
-// With g = w dy and xhat = (x - mean) rstd, the reference's three terms (layernorm.py:58-73) collapse to
+// Backward.  With g = w dy and xhat = (x - mean) rstd, the reference's three terms (layernorm.py:58-73) collapse to
 //   dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)):  two row sums, taken with ONE pair of barriers.
-template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) void layernorm_bwd_rows(
-    const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
-    const float* __restrict__ Mean, const float* __restrict__ Rstd, float* __restrict__ dX,
-    float* __restrict__ part_dw, float* __restrict__ part_db, int64_t rows, int64_t cols,
-    const float* __restrict__ dXadd, int nt) {
-    constexpr int RPB = (TPR >= 256) ? 1 : 256 / TPR;
-    constexpr int NW = TPR / 64;
-    __shared__ float red[32];
-    __shared__ float4 fin_lds[RPB > 1 ? 256 : 1];
-    const int t = threadIdx.x % TPR;
-    const int rslot = RPB > 1 ? threadIdx.x / TPR : 0;
-    RowTile<TPR, NV, VEC> wt, adw, adb;
-    if (w) wt.load(w, cols, t, 0.f);
-#pragma unroll
-    for (int e = 0; e < wt.NE; ++e) {
-        adw.x[e] = adb.x[e] = 0.f;
-        if (!w) wt.x[e] = 1.f;
+struct LayerNorm {
+    const float* __restrict__ Mean;
+    const float* __restrict__ Rstd;
+    static constexpr bool kOptional = true;
+    struct Row { float mu, rs; };
+    __device__ __forceinline__ Row stats(int64_t r) const { return {Mean[r], Rstd[r]}; }
+    // x <- xhat (padding lanes: dy = 0 there, so nothing below sees them); dw/db partials += this element; g <- dX_hat = w * dy
+    __device__ __forceinline__ void accumulate(const Row& st, float& x, float& g, float w, float& adw, float& adb, float& s1,
+                                               float& s2) const {
+        x = (x - st.mu) * st.rs;
+        adb += g;
+        adw += g * x;
+        g *= w;
+        s1 += g;
+        s2 += g * x;
     }
-    const float invN = 1.0f / (float)cols;
-    const int64_t step = (int64_t)gridDim.x * RPB;
-    constexpr bool PRE = TPR < 1024;   // (see rmsnorm_bwd_rows)
-    RowTile<TPR, NV, VEC> x0, g0, nx, ng;
-    const int64_t first = (int64_t)blockIdx.x * RPB + rslot;
-    if constexpr (PRE) {
-        if (first < rows) {
-            x0.load(X + first * cols, cols, t, 0.f, nt);
-            g0.load(dY + first * cols, cols, t, 0.f, nt);
-        }
-    }
-    for (int64_t r0 = first; r0 < rows; r0 += step) {
-        if constexpr (PRE) {
-            const int64_t n0 = r0 + step;
-            if (n0 < rows) {
-                nx.load(X + n0 * cols, cols, t, 0.f, nt);
-                ng.load(dY + n0 * cols, cols, t, 0.f, nt);
-            }
-        } else {
-            x0.load(X + r0 * cols, cols, t, 0.f, nt);
-            g0.load(dY + r0 * cols, cols, t, 0.f, nt);
-        }
-        const float mu = Mean[r0], rs = Rstd[r0];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < x0.NE; ++e) {
-            x0.x[e] = (x0.x[e] - mu) * rs;            // xhat (padding lanes: dy = 0 there, so nothing below sees them)
-            adb.x[e] += g0.x[e];
-            adw.x[e] += g0.x[e] * x0.x[e];
-            g0.x[e] *= wt.x[e];                       // dX_hat = w * dy
-            s1 += g0.x[e];
-            s2 += g0.x[e] * x0.x[e];
-        }
+    template <int NW>
+    __device__ __forceinline__ static void reduce(float& s1, float& s2, float invN, float* red) {
         if constexpr (NW == 1) { s1 = wave_sum(s1); s2 = wave_sum(s2); }
         else block_sum2<NW>(s1, s2, red);
         s1 *= invN;
         s2 *= invN;
-#pragma unroll
-        for (int e = 0; e < x0.NE; ++e) g0.x[e] = (g0.x[e] - s1 - x0.x[e] * s2) * rs;
-        if (dXadd) {   // dX = layernorm gradient + an already accumulated gradient of X (x0 is dead: reuse it).  __fadd_rn: a
-            // separately rounded add the compiler may not contract into the multiply above, so that the Ex entry returns
-            // EXACTLY (plain entry's dX) + addend, bit for bit
-            x0.load(dXadd + r0 * cols, cols, t, 0.f);
-#pragma unroll
-            for (int e = 0; e < x0.NE; ++e) g0.x[e] = __fadd_rn(g0.x[e], x0.x[e]);
-        }
-        g0.store(dX + r0 * cols, cols, t);
-        if constexpr (PRE) {
-#pragma unroll
-            for (int e = 0; e < x0.NE; ++e) { x0.x[e] = nx.x[e]; g0.x[e] = ng.x[e]; }
-        }
     }
-    if (!part_dw && !part_db) return;      // elementwise_affine=False (uniform for the whole grid)
-    if constexpr (RPB > 1) {
-        float* xch = reinterpret_cast<float*>(fin_lds);
-        constexpr int NE = NV * 4;
-        constexpr int EPP = (1024 / (3 * 64)) < NE ? (1024 / (3 * 64)) : NE;
-        auto fold = [&](RowTile<TPR, NV, VEC>& acc) {
-#pragma unroll
-            for (int e0 = 0; e0 < NE; e0 += EPP) {
-                __syncthreads();
-                if (rslot > 0) {
-#pragma unroll
-                    for (int e = 0; e < EPP; ++e)
-                        if (e0 + e < NE) xch[((rslot - 1) * EPP + e) * 64 + t] = acc.x[e0 + e];
-                }
-                __syncthreads();
-                if (rslot == 0) {
-#pragma unroll
-                    for (int e = 0; e < EPP; ++e)
-                        if (e0 + e < NE)
-                            acc.x[e0 + e] += (xch[(0 * EPP + e) * 64 + t] + xch[(1 * EPP + e) * 64 + t]) + xch[(2 * EPP + e) * 64 + t];
-                }
-            }
-        };
-        if (part_dw) fold(adw);
-        if (part_db) fold(adb);
-        __syncthreads();
+    __device__ __forceinline__ float dx(const Row& st, float g, float xhat, float s1, float s2) const {
+        return (g - s1 - xhat * s2) * st.rs;
     }
-    if (rslot == 0) {
-        if (part_dw) adw.store(part_dw + (int64_t)blockIdx.x * cols, cols, t);
-        if (part_db) adb.store(part_db + (int64_t)blockIdx.x * cols, cols, t);
-    }
+    // __fadd_rn: a separately rounded add the compiler may not contract into the multiply before it, so that the Ex entry
+    // returns EXACTLY (plain entry's dX) + addend, bit for bit
+    __device__ __forceinline__ static float add(float v, float a) { return __fadd_rn(v, a); }
+    __device__ __forceinline__ float xhat(float x, int64_t r) const { return (x - Mean[r]) * Rstd[r]; }
+};
+
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__(row_block(TPR)) void layernorm_bwd_rows(
+    const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ w,
+    const float* __restrict__ Mean, const float* __restrict__ Rstd, float* __restrict__ dX,
+    float* __restrict__ part_dw, float* __restrict__ part_db, int64_t rows, int64_t cols,
+    const float* __restrict__ dXadd, int nt) {
+    norm_bwd_rows<LayerNorm, TPR, NV, VEC>(LayerNorm{Mean, Rstd}, dY, X, w, dX, part_dw, part_db, rows, cols, dXadd, nt);
 }
 
 // ---- LayerNorm for rows wider than the register tile (cols > 16384): looped, one block per row ------------------------
@@ -893,23 +885,11 @@ __global__ __launch_bounds__(1024) void layernorm_bwd_dx_looped(const float* __r
         dX[row * cols + i] = v;
     }
 }
-// dw[c] = sum_r dy[r,c] xhat[r,c], db[c] = sum_r dy[r,c]: thread per column, rows split over gridDim.y (rmsnorm_bwd_dwdb_cols)
 __global__ __launch_bounds__(256) void layernorm_bwd_dwdb_cols(const float* __restrict__ dY, const float* __restrict__ X,
                                                                const float* __restrict__ Mean, const float* __restrict__ Rstd,
                                                                float* __restrict__ part_dw, float* __restrict__ part_db,
                                                                int64_t rows, int64_t cols, int64_t rows_per_block) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= cols) return;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-    const int64_t r1 = min(rows, r0 + rows_per_block);
-    float aw = 0.f, ab = 0.f;
-    for (int64_t r = r0; r < r1; ++r) {
-        const float g = dY[r * cols + c];
-        aw += g * ((X[r * cols + c] - Mean[r]) * Rstd[r]);
-        ab += g;
-    }
-    if (part_dw) part_dw[(int64_t)blockIdx.y * cols + c] = aw;
-    if (part_db) part_db[(int64_t)blockIdx.y * cols + c] = ab;
+    norm_bwd_dwdb_cols(LayerNorm{Mean, Rstd}, dY, X, part_dw, part_db, rows, cols, rows_per_block);
 }
 
 // =================================================================================================
@@ -1105,9 +1085,9 @@ __device__ __forceinline__ void ce_epilogue(const CeArgs& a, float lsum, float d
 #define NNHIP_CE_WAVES 4
 #endif
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__((TPR >= 256) ? TPR : 256) __attribute__((amdgpu_waves_per_eu(NV <= 4 && VEC ? NNHIP_CE_WAVES : 4)))
+__global__ __launch_bounds__(row_block(TPR)) __attribute__((amdgpu_waves_per_eu(NV <= 4 && VEC ? NNHIP_CE_WAVES : 4)))
 void ce_rows_kernel(const CeArgs a) {
-    constexpr int BS = (TPR >= 256) ? TPR : 256;
+    constexpr int BS = row_block(TPR);
     constexpr int RPB = BS / TPR;
     __shared__ float red[32];
     __shared__ int ired[17];
@@ -1706,43 +1686,31 @@ static int row_streaming(int64_t rows, int64_t cols, int64_t ld) {
     return (rows * cols * 4 >= ((int64_t)128 << 20) && ((ld * 4) & 127) == 0) ? 1 : 0;
 }
 
-// Row-kernel dispatch: pick (TPR, NV) from the row width.
-#define ROW_DISPATCH(KERNEL, cols, vec, rows, st, ...)                                              \
-    do {                                                                                            \
-        const int64_t _c = (cols);                                                                  \
-        if (_c <= 256) { ROW_LAUNCH(KERNEL, 64, 1, vec, rows, st, __VA_ARGS__); }                   \
-        else if (_c <= 512) { ROW_LAUNCH(KERNEL, 64, 2, vec, rows, st, __VA_ARGS__); }              \
-        else if (_c <= 1024) { ROW_LAUNCH(KERNEL, 64, 4, vec, rows, st, __VA_ARGS__); }             \
-        else if (_c <= 4096) { ROW_LAUNCH(KERNEL, 256, 4, vec, rows, st, __VA_ARGS__); }            \
-        else if (_c <= 8192) { ROW_LAUNCH(KERNEL, 256, 8, vec, rows, st, __VA_ARGS__); }            \
-        else { ROW_LAUNCH(KERNEL, 1024, 4, vec, rows, st, __VA_ARGS__); }                           \
-    } while (0)
-#define ROW_LAUNCH(KERNEL, TPR, NV, vec, rows, st, ...)                                             \
-    do {                                                                                            \
-        constexpr int _rpb = (TPR >= 256) ? 1 : 256 / TPR;                                          \
-        constexpr int _bs = (TPR >= 256) ? TPR : 256;                                               \
-        const unsigned _g = (unsigned)ceil_div((rows), _rpb);                                       \
-        if (vec) hipLaunchKernelGGL((KERNEL<TPR, NV, true>), dim3(_g), dim3(_bs), 0, st, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL<TPR, NV, false>), dim3(_g), dim3(_bs), 0, st, __VA_ARGS__);     \
-    } while (0)
-
-// Persistent variants: the caller fixes the number of blocks.
-#define ROW_DISPATCH_GRID(KERNEL, cols, vec, nblk, st, ...)                                         \
-    do {                                                                                            \
-        const int64_t _c = (cols);                                                                  \
-        if (_c <= 256) { ROW_LAUNCH_GRID(KERNEL, 64, 1, vec, nblk, st, __VA_ARGS__); }              \
-        else if (_c <= 512) { ROW_LAUNCH_GRID(KERNEL, 64, 2, vec, nblk, st, __VA_ARGS__); }         \
-        else if (_c <= 1024) { ROW_LAUNCH_GRID(KERNEL, 64, 4, vec, nblk, st, __VA_ARGS__); }        \
-        else if (_c <= 4096) { ROW_LAUNCH_GRID(KERNEL, 256, 4, vec, nblk, st, __VA_ARGS__); }       \
-        else if (_c <= 8192) { ROW_LAUNCH_GRID(KERNEL, 256, 8, vec, nblk, st, __VA_ARGS__); }       \
-        else { ROW_LAUNCH_GRID(KERNEL, 1024, 4, vec, nblk, st, __VA_ARGS__); }                      \
-    } while (0)
-#define ROW_LAUNCH_GRID(KERNEL, TPR, NV, vec, nblk, st, ...)                                        \
-    do {                                                                                            \
-        constexpr int _bs = (TPR >= 256) ? TPR : 256;                                               \
-        if (vec) hipLaunchKernelGGL((KERNEL<TPR, NV, true>), dim3((unsigned)(nblk)), dim3(_bs), 0, st, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL<TPR, NV, false>), dim3((unsigned)(nblk)), dim3(_bs), 0, st, __VA_ARGS__);     \
-    } while (0)
+// Row-kernel dispatch: the tier table, row width -> (TPR, NV).  f(tpr, nv, vec) is called with integral_constants, so it
+// can name the instantiation: KERNEL<tpr, nv, vec>.
+template <class F>
+static void row_tier(int64_t cols, bool vec, F&& f) {
+    auto tier = [&](auto tpr, auto nv) {
+        if (vec) f(tpr, nv, std::true_type{});
+        else f(tpr, nv, std::false_type{});
+    };
+    using std::integral_constant;
+    if (cols <= 256) tier(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    else if (cols <= 512) tier(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+    else if (cols <= 1024) tier(integral_constant<int, 64>{}, integral_constant<int, 4>{});
+    else if (cols <= 4096) tier(integral_constant<int, 256>{}, integral_constant<int, 4>{});
+    else if (cols <= 8192) tier(integral_constant<int, 256>{}, integral_constant<int, 8>{});
+    else tier(integral_constant<int, 1024>{}, integral_constant<int, 4>{});
+}
+// One block per row_rpb(TPR) rows / persistent: the caller fixes the number of blocks.
+template <int TPR, class K, class... A>
+static void row_launch_grid(K kernel, int64_t nblk, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(row_block(TPR)), 0, st, args...);
+}
+template <int TPR, class K, class... A>
+static void row_launch(K kernel, int64_t rows, hipStream_t st, A... args) {
+    row_launch_grid<TPR>(kernel, ceil_div(rows, row_rpb(TPR)), st, args...);
+}
 
 // Resident blocks of a kernel instantiation on the whole device (occupancy query, cached per instantiation): the
 // persistent kernels size their grids in multiples of it so no block waits for a slot behind a full-length one.
@@ -1767,23 +1735,105 @@ static int resident_slots_impl(const void* kernel, int bs) {
 }
 template <class K>
 static int resident_slots(K kernel, int bs) { return resident_slots_impl(reinterpret_cast<const void*>(kernel), bs); }
-#define ROW_DISPATCH_SLOTS(KERNEL, cols, vec, OUT)                                                  \
-    do {                                                                                            \
-        const int64_t _c = (cols);                                                                  \
-        if (_c <= 256) { ROW_SLOTS(KERNEL, 64, 1, vec, OUT); }                                      \
-        else if (_c <= 512) { ROW_SLOTS(KERNEL, 64, 2, vec, OUT); }                                 \
-        else if (_c <= 1024) { ROW_SLOTS(KERNEL, 64, 4, vec, OUT); }                                \
-        else if (_c <= 4096) { ROW_SLOTS(KERNEL, 256, 4, vec, OUT); }                               \
-        else if (_c <= 8192) { ROW_SLOTS(KERNEL, 256, 8, vec, OUT); }                               \
-        else { ROW_SLOTS(KERNEL, 1024, 4, vec, OUT); }                                              \
-    } while (0)
-#define ROW_SLOTS(KERNEL, TPR, NV, vec, OUT)                                                        \
-    do {                                                                                            \
-        constexpr int _bs = (TPR >= 256) ? TPR : 256;                                               \
-        OUT = (vec) ? resident_slots(KERNEL<TPR, NV, true>, _bs) : resident_slots(KERNEL<TPR, NV, false>, _bs); \
-    } while (0)
 
 constexpr int64_t kMaxRegRow = 16384;
+
+// ---- the host side of both norm backward entries ----------------------------------------------------------------------
+// What an entry hands to norm_backward (its `Entry`): its name for the messages, its kernels and their launch-check names.  The kernels
+// of the two norms take the same arguments except for the saved row statistics (X_std / mean, rstd), passed on as `stat...`.
+struct RmsNormBackward {
+    static constexpr const char* entry = "nnhipRMSNormBackward";
+    static constexpr const char *rows_name = "rmsnorm_backward", *dx_looped_name = "rmsnorm_bwd_dx_looped", *cols_name = "rmsnorm_bwd_dwdb_cols";
+    static constexpr const char* grid_mult_env = "NNHIP_RMS_GRID_MULT";      // developer switch: scales the persistent grid
+    template <int TPR, int NV, bool VEC> static auto rows() { return rmsnorm_bwd_rows<TPR, NV, VEC>; }
+    static auto dx_looped() { return rmsnorm_bwd_dx_looped; }
+    static auto cols() { return rmsnorm_bwd_dwdb_cols; }
+};
+struct LayerNormBackward {
+    static constexpr const char* entry = "nnhipLayerNormBackward";
+    static constexpr const char *rows_name = "layernorm_backward", *dx_looped_name = "layernorm_bwd_dx_looped", *cols_name = "layernorm_bwd_dwdb_cols";
+    static constexpr const char* grid_mult_env = nullptr;
+    template <int TPR, int NV, bool VEC> static auto rows() { return layernorm_bwd_rows<TPR, NV, VEC>; }
+    static auto dx_looped() { return layernorm_bwd_dx_looped; }
+    static auto cols() { return layernorm_bwd_dwdb_cols; }
+};
+
+// dX (+ addend), and dW / dB where present (the entry has checked which of them may be null).
+template <class Entry, class... Stat>
+static int norm_backward(const float* dY, const float* X, const float* weight, const float* dX_addend, float* dX, float* dW,
+                         float* dB, int64_t rows, int64_t cols, hipStream_t st, Stat... stat) {
+    const int nparts = (dW ? 1 : 0) + (dB ? 1 : 0);
+    if (cols > kMaxRegRow) {
+        // wide rows: looped dX kernel + a column pass for dw/db (partials over row chunks, then the in-launch column sum)
+        if (rows > 0) {
+            hipLaunchKernelGGL(Entry::dx_looped(), dim3((unsigned)rows), dim3(1024), 0, st, dY, X, weight, stat..., dX, cols, dX_addend);
+            NNHIP_LAUNCH_CHECK(Entry::dx_looped_name);
+        }
+        if (nparts == 0) return 0;
+        const int64_t col_blocks = ceil_div(cols, 256);
+        int64_t ry = 1024 / col_blocks;
+        if (ry > ceil_div(rows > 0 ? rows : 1, 8)) ry = ceil_div(rows > 0 ? rows : 1, 8);
+        if (ry < 1) ry = 1;
+        const int64_t rpb = ceil_div(rows > 0 ? rows : 1, ry);
+        ry = ceil_div(rows > 0 ? rows : 1, rpb);
+        const size_t pf = ((size_t)ry * cols + 3) / 4 * 4;
+        float* part = static_cast<float*>(workspace(pf * nparts * sizeof(float) + 2 * (size_t)cols * 64 * sizeof(float)));
+        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "%s: workspace allocation failed", Entry::entry);
+        float* pdw = dW ? part : nullptr;
+        float* pdb = dB ? part + (dW ? pf : 0) : nullptr;
+        hipLaunchKernelGGL(Entry::cols(), dim3((unsigned)col_blocks, (unsigned)ry), dim3(256), 0, st, dY, X, stat..., pdw, pdb, rows, cols, rpb);
+        NNHIP_LAUNCH_CHECK(Entry::cols_name);
+        float* scr = part + pf * nparts;
+        auto finish = [&](const float* p, float* out) -> int {
+            const ColsumPlan cp = colsum_plan(p, out, ry, cols, cols);
+            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "%s: column-sum scratch too small", Entry::entry);
+            return colsum_run(cp, p, ry, cols, cols, out, scr, st);
+        };
+        if (int rc = dW ? finish(pdw, dW) : 0) return rc;
+        if (int rc = dB ? finish(pdb, dB) : 0) return rc;
+        return 0;
+    }
+    const bool vec = aligned16(dY) && aligned16(X) && aligned16(weight) && aligned16(dX) && aligned16(dX_addend) &&
+                     aligned16(dW) && aligned16(dB) && cols % 4 == 0;
+    // persistent grid = the blocks that are resident at once (occupancy query), each accumulating dw/db partials over
+    // its rows
+    const int rpb = cols <= 1024 ? 4 : 1;
+    int64_t nblk = ceil_div(rows > 0 ? rows : 1, rpb);
+    int slots = 1024;
+    row_tier(cols, vec, [&](auto tpr, auto nv, auto v) { slots = resident_slots(Entry::template rows<tpr, nv, v>(), row_block(tpr)); });
+    if constexpr (Entry::grid_mult_env != nullptr) {
+        static const double mult = []() { const char* e = getenv(Entry::grid_mult_env); return e ? atof(e) : 1.0; }();
+        slots = (int)(slots * mult);
+    }
+    if (slots < 1) slots = 1;
+    if (nblk > slots) nblk = slots;
+    const size_t part_floats = ((size_t)nblk * cols + 63) / 64 * 64;
+    bool deferred = false;
+    float* part = nullptr;
+    if (nparts) {
+        // inside Tensor.backward() the finishing column sums wait for the flush (one launch for every norm of the pass)
+        int rcq = 0;
+        part = colsum_partials(part_floats * nparts, nparts, fin_sw(cols, vec), vec, st, &deferred, &rcq);
+        if (rcq) return rcq;
+        if (!part) part = static_cast<float*>(workspace(part_floats * nparts * sizeof(float)));
+        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "%s: workspace allocation failed", Entry::entry);
+    }
+    float* part_dw = dW ? part : nullptr;
+    float* part_db = dB ? part + (dW ? part_floats : 0) : nullptr;
+    row_tier(cols, vec, [&](auto tpr, auto nv, auto v) {
+        row_launch_grid<tpr>(Entry::template rows<tpr, nv, v>(), nblk, st, dY, X, weight, stat..., dX, part_dw, part_db, rows, cols, dX_addend,
+                             row_streaming(rows, cols, cols));
+    });
+    NNHIP_LAUNCH_CHECK(Entry::rows_name);
+    if (nparts == 0) return 0;
+    if (deferred) {
+        if (dW) colsum_queue(part_dw, dW, nblk, cols);
+        if (dB) colsum_queue(part_db, dB, nblk, cols);
+        return 0;
+    }
+    if (dW) return colsum_tall(part_dw, dW, part_db, dB, nblk, cols, vec, st);
+    return colsum_tall(part_db, dB, nullptr, nullptr, nblk, cols, vec, st);
+}
 
 }  // namespace nnhip
 
@@ -1804,7 +1854,9 @@ extern "C" int nnhipSoftmaxForward(float* out, const float* in, int64_t num_slic
         hipLaunchKernelGGL(softmax_fwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, out, in, slice_size);
     } else {
         const bool vec = aligned16(out) && aligned16(in) && slice_size % 4 == 0;
-        ROW_DISPATCH(softmax_fwd_rows, slice_size, vec, num_slices, st, out, in, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(softmax_fwd_rows<tpr, nv, v>, num_slices, st, out, in, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        });
     }
     NNHIP_LAUNCH_CHECK("softmax_forward");
     return 0;
@@ -1824,7 +1876,9 @@ extern "C" int nnhipSoftmaxBackward(float* dX, const float* dY, const float* Y, 
         hipLaunchKernelGGL(softmax_bwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, dX, dY, Y, slice_size);
     } else {
         const bool vec = aligned16(dX) && aligned16(dY) && aligned16(Y) && slice_size % 4 == 0;
-        ROW_DISPATCH(softmax_bwd_rows, slice_size, vec, num_slices, st, dX, dY, Y, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(softmax_bwd_rows<tpr, nv, v>, num_slices, st, dX, dY, Y, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        });
     }
     NNHIP_LAUNCH_CHECK("softmax_backward");
     return 0;
@@ -1843,7 +1897,9 @@ extern "C" int nnhipRMSNormForward(const float* X, const float* weight, const fl
     } else {
         const bool vec = aligned16(X) && aligned16(Y) && aligned16(weight) && (!bias || aligned16(bias)) &&
                          (!X_norm || aligned16(X_norm)) && cols % 4 == 0;
-        ROW_DISPATCH(rmsnorm_fwd_rows, cols, vec, rows, st, X, weight, bias, Y, X_std, X_norm, rows, cols, eps, row_streaming(rows, cols, cols));
+        row_tier(cols, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(rmsnorm_fwd_rows<tpr, nv, v>, rows, st, X, weight, bias, Y, X_std, X_norm, rows, cols, eps, row_streaming(rows, cols, cols));
+        });
     }
     NNHIP_LAUNCH_CHECK("rmsnorm_forward");
     return 0;
@@ -1865,69 +1921,7 @@ extern "C" int nnhipRMSNormBackwardEx(const float* dY, const float* X, const flo
     if (cols == 0) return 0;
     NNHIP_CHECK_ARG(dY && X && weight && X_std && dX && dW, NNHIP_EINVAL,
                     "nnhipRMSNormBackward: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (cols > kMaxRegRow) {
-        // wide rows: looped dX kernel + a column pass for dw/db (partials over row chunks, then the in-launch column sum)
-        if (rows > 0) {
-            hipLaunchKernelGGL(rmsnorm_bwd_dx_looped, dim3((unsigned)rows), dim3(1024), 0, st, dY, X, weight, X_std, dX, cols, dX_addend);
-            NNHIP_LAUNCH_CHECK("rmsnorm_bwd_dx_looped");
-        }
-        const int64_t col_blocks = ceil_div(cols, 256);
-        int64_t ry = 1024 / col_blocks;
-        if (ry > ceil_div(rows > 0 ? rows : 1, 8)) ry = ceil_div(rows > 0 ? rows : 1, 8);
-        if (ry < 1) ry = 1;
-        const int64_t rpb = ceil_div(rows > 0 ? rows : 1, ry);
-        ry = ceil_div(rows > 0 ? rows : 1, rpb);
-        const size_t pf = ((size_t)ry * cols + 3) / 4 * 4;
-        float* part = static_cast<float*>(workspace(pf * (db ? 2 : 1) * sizeof(float) + 2 * (size_t)cols * 64 * sizeof(float)));
-        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipRMSNormBackward: workspace allocation failed");
-        float* pdb = db ? part + pf : nullptr;
-        hipLaunchKernelGGL(rmsnorm_bwd_dwdb_cols, dim3((unsigned)col_blocks, (unsigned)ry), dim3(256), 0, st, dY, X, X_std, part, pdb, rows, cols, rpb);
-        NNHIP_LAUNCH_CHECK("rmsnorm_bwd_dwdb_cols");
-        float* scr = part + pf * (db ? 2 : 1);
-        {
-            const ColsumPlan cp = colsum_plan(part, dW, ry, cols, cols);
-            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "nnhipRMSNormBackward: column-sum scratch too small");
-            if (int rc = colsum_run(cp, part, ry, cols, cols, dW, scr, st)) return rc;
-        }
-        if (db) {
-            const ColsumPlan cp = colsum_plan(pdb, db, ry, cols, cols);
-            if (int rc = colsum_run(cp, pdb, ry, cols, cols, db, scr, st)) return rc;
-        }
-        return 0;
-    }
-    const bool vec = aligned16(dY) && aligned16(X) && aligned16(weight) && aligned16(dX) && aligned16(dX_addend) &&
-                     aligned16(dW) && aligned16(db) && cols % 4 == 0;
-    // persistent grid = the blocks that are resident at once (occupancy query), each accumulating dw/db partials over
-    // its rows
-    const int rpb = cols <= 1024 ? 4 : 1;
-    int64_t nblk = ceil_div(rows > 0 ? rows : 1, rpb);
-    int slots = 1024;
-    ROW_DISPATCH_SLOTS(rmsnorm_bwd_rows, cols, vec, slots);
-    {
-        static const double mult = []() { const char* e = getenv("NNHIP_RMS_GRID_MULT"); return e ? atof(e) : 1.0; }();
-        slots = (int)(slots * mult);
-        if (slots < 1) slots = 1;
-    }
-    if (nblk > slots) nblk = slots;
-    const size_t part_floats = ((size_t)nblk * cols + 63) / 64 * 64;
-    // inside Tensor.backward() the finishing column sums wait for the flush (one launch for every RMSNorm of the pass)
-    bool deferred = false;
-    int rcq = 0;
-    float* part = colsum_partials(part_floats * (db ? 2 : 1), db ? 2 : 1, fin_sw(cols, vec), vec, st, &deferred, &rcq);
-    if (rcq) return rcq;
-    if (!part) part = static_cast<float*>(workspace(part_floats * (db ? 2 : 1) * sizeof(float)));
-    NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipRMSNormBackward: workspace allocation failed");
-    float* part_dw = part;
-    float* part_db = db ? part + part_floats : nullptr;
-    ROW_DISPATCH_GRID(rmsnorm_bwd_rows, cols, vec, nblk, st, dY, X, weight, X_std, dX, part_dw, part_db, rows, cols, dX_addend, row_streaming(rows, cols, cols));
-    NNHIP_LAUNCH_CHECK("rmsnorm_backward");
-    if (deferred) {
-        colsum_queue(part_dw, dW, nblk, cols);
-        if (db) colsum_queue(part_db, db, nblk, cols);
-        return 0;
-    }
-    return colsum_tall(part_dw, dW, part_db, db, nblk, cols, vec, st);
+    return norm_backward<RmsNormBackward>(dY, X, weight, dX_addend, dX, dW, db, rows, cols, (hipStream_t)s, X_std);
 }
 
 // ---- LayerNorm (ABI 212) ------------------------------------------------------------------------
@@ -1943,7 +1937,9 @@ extern "C" int nnhipLayerNormForward(const float* X, const float* weight, const 
         hipLaunchKernelGGL(layernorm_fwd_looped, dim3((unsigned)rows), dim3(1024), 0, st, X, weight, bias, Y, mean, rstd, cols, eps);
     } else {
         const bool vec = aligned16(X) && aligned16(Y) && aligned16(weight) && aligned16(bias) && cols % 4 == 0;
-        ROW_DISPATCH(layernorm_fwd_rows, cols, vec, rows, st, X, weight, bias, Y, mean, rstd, rows, cols, eps, row_streaming(rows, cols, cols));
+        row_tier(cols, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(layernorm_fwd_rows<tpr, nv, v>, rows, st, X, weight, bias, Y, mean, rstd, rows, cols, eps, row_streaming(rows, cols, cols));
+        });
     }
     NNHIP_LAUNCH_CHECK("layernorm_forward");
     return 0;
@@ -1963,72 +1959,7 @@ extern "C" int nnhipLayerNormBackwardEx(const float* dY, const float* X, const f
     NNHIP_CHECK_ARG(dY && X && mean && rstd && dX, NNHIP_EINVAL, "nnhipLayerNormBackward: null pointer");
     NNHIP_CHECK_ARG(aligned4(dY) && aligned4(X) && aligned4(weight) && aligned4(mean) && aligned4(rstd) && aligned4(dX_addend) &&
                     aligned4(dX) && aligned4(dW) && aligned4(dB), NNHIP_EALIGN, "nnhipLayerNormBackward: misaligned pointer");
-    hipStream_t st = (hipStream_t)s;
-    const int nparts = (dW ? 1 : 0) + (dB ? 1 : 0);
-    if (cols > kMaxRegRow) {
-        if (rows > 0) {
-            hipLaunchKernelGGL(layernorm_bwd_dx_looped, dim3((unsigned)rows), dim3(1024), 0, st, dY, X, weight, mean, rstd, dX, cols, dX_addend);
-            NNHIP_LAUNCH_CHECK("layernorm_bwd_dx_looped");
-        }
-        if (nparts == 0) return 0;
-        const int64_t col_blocks = ceil_div(cols, 256);
-        int64_t ry = 1024 / col_blocks;
-        if (ry > ceil_div(rows > 0 ? rows : 1, 8)) ry = ceil_div(rows > 0 ? rows : 1, 8);
-        if (ry < 1) ry = 1;
-        const int64_t rpb = ceil_div(rows > 0 ? rows : 1, ry);
-        ry = ceil_div(rows > 0 ? rows : 1, rpb);
-        const size_t pf = ((size_t)ry * cols + 3) / 4 * 4;
-        float* part = static_cast<float*>(workspace(pf * nparts * sizeof(float) + 2 * (size_t)cols * 64 * sizeof(float)));
-        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipLayerNormBackward: workspace allocation failed");
-        float* pdw = dW ? part : nullptr;
-        float* pdb = dB ? part + (dW ? pf : 0) : nullptr;
-        hipLaunchKernelGGL(layernorm_bwd_dwdb_cols, dim3((unsigned)col_blocks, (unsigned)ry), dim3(256), 0, st, dY, X, mean, rstd, pdw, pdb, rows, cols, rpb);
-        NNHIP_LAUNCH_CHECK("layernorm_bwd_dwdb_cols");
-        float* scr = part + pf * nparts;
-        if (dW) {
-            const ColsumPlan cp = colsum_plan(pdw, dW, ry, cols, cols);
-            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "nnhipLayerNormBackward: column-sum scratch too small");
-            if (int rc = colsum_run(cp, pdw, ry, cols, cols, dW, scr, st)) return rc;
-        }
-        if (dB) {
-            const ColsumPlan cp = colsum_plan(pdb, dB, ry, cols, cols);
-            NNHIP_CHECK_ARG(cp.scratch_floats <= (size_t)cols * 64, NNHIP_ENOMEM, "nnhipLayerNormBackward: column-sum scratch too small");
-            if (int rc = colsum_run(cp, pdb, ry, cols, cols, dB, scr, st)) return rc;
-        }
-        return 0;
-    }
-    const bool vec = aligned16(dY) && aligned16(X) && aligned16(weight) && aligned16(dX) && aligned16(dX_addend) &&
-                     aligned16(dW) && aligned16(dB) && cols % 4 == 0;
-    // persistent grid = the blocks that are resident at once, each accumulating dw/db partials over its rows (nnhipRMSNormBackwardEx)
-    const int rpb = cols <= 1024 ? 4 : 1;
-    int64_t nblk = ceil_div(rows > 0 ? rows : 1, rpb);
-    int slots = 1024;
-    ROW_DISPATCH_SLOTS(layernorm_bwd_rows, cols, vec, slots);
-    if (slots < 1) slots = 1;
-    if (nblk > slots) nblk = slots;
-    const size_t part_floats = ((size_t)nblk * cols + 63) / 64 * 64;
-    bool deferred = false;
-    float* part = nullptr;
-    if (nparts) {
-        // inside Tensor.backward() the finishing column sums wait for the flush, in the RMSNorm queue (one launch per pass)
-        int rcq = 0;
-        part = colsum_partials(part_floats * nparts, nparts, fin_sw(cols, vec), vec, st, &deferred, &rcq);
-        if (rcq) return rcq;
-        if (!part) part = static_cast<float*>(workspace(part_floats * nparts * sizeof(float)));
-        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipLayerNormBackward: workspace allocation failed");
-    }
-    float* part_dw = dW ? part : nullptr;
-    float* part_db = dB ? part + (dW ? part_floats : 0) : nullptr;
-    ROW_DISPATCH_GRID(layernorm_bwd_rows, cols, vec, nblk, st, dY, X, weight, mean, rstd, dX, part_dw, part_db, rows, cols, dX_addend, row_streaming(rows, cols, cols));
-    NNHIP_LAUNCH_CHECK("layernorm_backward");
-    if (nparts == 0) return 0;
-    if (deferred) {
-        if (dW) colsum_queue(part_dw, dW, nblk, cols);
-        if (dB) colsum_queue(part_db, dB, nblk, cols);
-        return 0;
-    }
-    if (dW) return colsum_tall(part_dw, dW, part_db, dB, nblk, cols, vec, st);
-    return colsum_tall(part_db, dB, nullptr, nullptr, nblk, cols, vec, st);
+    return norm_backward<LayerNormBackward>(dY, X, weight, dX_addend, dX, dW, dB, rows, cols, (hipStream_t)s, mean, rstd);
 }
 
 // ---- CrossEntropy -------------------------------------------------------------------------------
@@ -2057,7 +1988,7 @@ static int ce_launch(CeArgs a, hipStream_t st) {
     // negligible
     int slots = 512;
     if (looped) slots = resident_slots(ce_looped_kernel, 1024);
-    else ROW_DISPATCH_SLOTS(ce_rows_kernel, a.cols, vec, slots);
+    else row_tier(a.cols, vec, [&](auto tpr, auto nv, auto v) { slots = resident_slots(ce_rows_kernel<tpr, nv, v>, row_block(tpr)); });
     if (nblk > (int64_t)slots) nblk = (int64_t)slots;       // one resident round: equal shares, one prologue per slot
     if (a.loss_out) {
         a.partial = static_cast<float*>(workspace((size_t)nblk * sizeof(float)));
@@ -2086,7 +2017,7 @@ static int ce_launch(CeArgs a, hipStream_t st) {
     if (looped) {
         hipLaunchKernelGGL(ce_looped_kernel, dim3((unsigned)nblk), dim3(1024), 0, st, a);
     } else {
-        ROW_DISPATCH_GRID(ce_rows_kernel, a.cols, vec, nblk, st, a);
+        row_tier(a.cols, vec, [&](auto tpr, auto nv, auto v) { row_launch_grid<tpr>(ce_rows_kernel<tpr, nv, v>, nblk, st, a); });
     }
     NNHIP_LAUNCH_CHECK("cross_entropy");
     return 0;
@@ -2313,7 +2244,9 @@ extern "C" int nnhipMaskedSoftmaxForwardEx(float* out, const float* in, const in
         hipLaunchKernelGGL(softmax_masked_fwd_looped, dim3((unsigned)rows), dim3(1024), 0, st, out, in, key_valid, Tk, H * Tq, Tq, scale, causal, dense_mask);
     } else {
         const bool vec = aligned16(out) && aligned16(in) && Tk % 4 == 0;
-        ROW_DISPATCH(softmax_masked_fwd_rows, Tk, vec, rows, st, out, in, key_valid, rows, Tk, H * Tq, Tq, scale, causal, dense_mask);
+        row_tier(Tk, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(softmax_masked_fwd_rows<tpr, nv, v>, rows, st, out, in, key_valid, rows, Tk, H * Tq, Tq, scale, causal, dense_mask);
+        });
     }
     NNHIP_LAUNCH_CHECK("softmax_masked_fwd_rows");
     return 0;
@@ -2337,7 +2270,9 @@ extern "C" int nnhipMaskedSoftmaxBackwardEx(float* dX, const float* dY, const fl
         hipLaunchKernelGGL(softmax_masked_bwd_looped, dim3((unsigned)rows), dim3(1024), 0, st, dX, dY, Y, key_valid, Tk, H * Tq, Tq, scale, causal, dense_mask);
     } else {
         const bool vec = aligned16(dX) && aligned16(dY) && aligned16(Y) && Tk % 4 == 0;
-        ROW_DISPATCH(softmax_masked_bwd_rows, Tk, vec, rows, st, dX, dY, Y, key_valid, rows, Tk, H * Tq, Tq, scale, causal, dense_mask);
+        row_tier(Tk, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(softmax_masked_bwd_rows<tpr, nv, v>, rows, st, dX, dY, Y, key_valid, rows, Tk, H * Tq, Tq, scale, causal, dense_mask);
+        });
     }
     NNHIP_LAUNCH_CHECK("softmax_masked_bwd_rows");
     return 0;

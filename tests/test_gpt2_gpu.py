@@ -174,6 +174,142 @@ def test_layernorm_residual_gradient_is_folded(hip):
     assert_close_scaled(host(x.grad), dXr, err_msg="dX")
 
 
+def layernorm_abi(rows, cols, seed, off=0):
+    """Inputs for the C entries, forward already run.  off: every buffer starts `off` floats into its allocation.  Returns the
+    device tensors, an allocator of such buffers, and the float64 (Y, dX, dw, db)."""
+    import torch
+    from neunet_hip.nn.experimental.layernorm import layernorm_forward as hip_fwd
+    rng = np.random.default_rng(seed)
+
+    def buf(*shape, fill=float("nan")):
+        return torch.full((int(np.prod(shape)) + off,), fill, device="cuda")[off:].view(*shape)
+
+    def put(a):
+        t = buf(*a.shape)
+        t.copy_(dev(a))
+        return t
+
+    X = put(rng.standard_normal((rows, cols)) * 1.3 + 0.2)
+    dY = put(rng.standard_normal((rows, cols)))
+    w, b = put(rng.uniform(0.5, 1.5, cols)), put(rng.uniform(-0.5, 0.5, cols))
+    Y, mean, rstd = buf(rows, cols), buf(rows), buf(rows)
+    hip_fwd(X, w, b, Y, mean, rstd, cols, 1e-5)
+    Yr, cache = layernorm_forward(host(X), host(w), host(b))
+    return dict(X=X, dY=dY, w=w, b=b, Y=Y, mean=mean, rstd=rstd), buf, (Yr,) + layernorm_backward(cache, host(dY))
+
+
+@pytest.mark.parametrize("cols,off", [(1024, 0), (1028, 0), (4096, 0), (8192, 0), (12000, 0), (16384, 0), (4096, 1)])
+def test_layernorm_every_tier_at_few_rows(hip, cols, off):
+    """Nine rows through every (threads per row, vectors per thread) tier of the register-tile kernels above 512 columns, forward
+    and backward, affine, against float64: 1024 is the widest wave-per-row tier, 1028 / 4096 / 8192 the block-per-row tiers with
+    the next row prefetched, 12000 / 16384 the 1024-thread tier without prefetch (16384: a full tile).  off = 1: every buffer
+    starts 4 bytes into its allocation -- 4-byte aligned, so the entries accept it, but not 16-byte aligned: the scalar variant of
+    the 4096 tier."""
+    from neunet_hip.nn.experimental.layernorm import layernorm_backward as hip_bwd
+    t, buf, (Yr, dXr, dwr, dbr) = layernorm_abi(9, cols, cols + off, off)
+    assert all(v.data_ptr() % 16 == 4 * off for v in t.values())
+    dX, dw, db = buf(9, cols), buf(cols), buf(cols)
+    hip_bwd(t["X"], t["w"], t["dY"], dX, dw, db, t["mean"], t["rstd"], cols)
+    np.testing.assert_allclose(host(t["Y"]), Yr, **TOL)
+    assert_close_scaled(host(dX), dXr, err_msg="dX")
+    assert_close_scaled(host(dw), dwr, err_msg="dw")
+    assert_close_scaled(host(db), dbr, err_msg="db")
+
+
+@pytest.mark.parametrize("rows,cols", [(37, 1000), (37, 1001), (5, 16388)])
+def test_layernorm_backward_nullable_outputs(hip, rows, cols):
+    """nnhipLayerNormBackward with dW, dB or both NULL.  (37, 1000) / (37, 1001): the register tile, vector and scalar variant (1001
+    is no multiple of 4), a ragged last 4-row block; (5, 16388): the looped dX kernel and the column pass.  What is asked for is BIT-identical to the call that asks for both, dX
+    is the same in all four, and a buffer that was not passed keeps its sentinel."""
+    import torch
+    from neunet_hip.nn.experimental.layernorm import layernorm_backward as hip_bwd
+    t, buf, (_, dXr, dwr, dbr) = layernorm_abi(rows, cols, rows + cols)
+    outs = {}
+    for want_w, want_b in [(True, True), (True, False), (False, True), (False, False)]:
+        dX, dw, db = buf(rows, cols), buf(cols, fill=123.0), buf(cols, fill=321.0)
+        hip_bwd(t["X"], t["w"], t["dY"], dX, dw if want_w else None, db if want_b else None, t["mean"], t["rstd"], cols)
+        outs[want_w, want_b] = (dX, dw, db)
+    dX0, dw0, db0 = outs[True, True]
+    assert_close_scaled(host(dX0), dXr, err_msg="dX")
+    assert_close_scaled(host(dw0), dwr, err_msg="dw")
+    assert_close_scaled(host(db0), dbr, err_msg="db")
+    for (want_w, want_b), (dX, dw, db) in outs.items():
+        assert torch.equal(dX, dX0), (want_w, want_b)
+        assert torch.equal(dw, dw0) if want_w else bool((dw == 123.0).all()), (want_w, want_b)
+        assert torch.equal(db, db0) if want_b else bool((db == 321.0).all()), (want_w, want_b)
+
+
+def test_norm_backward_deferred_column_sums_interleaved(hip):
+    """The mirror of test_rmsnorm_backward_deferred_column_sums for the queue that RMSNorm and LayerNorm share: inside one
+    nnhipWeightGradDefer window their backward calls interleave -- LayerNorm with both, one and none of dW / dB.  The queue holds
+    jobs of one width class: the 512-wide job flushes the 4096-wide one before it (another slice width), (33, 1000) joins the
+    512-wide jobs (same slice width, vector), and the last job, 1001 wide (no multiple of 4: the scalar class), flushes them all
+    while LayerNorm jobs are queued.  dX is there at once; the dW / dB of a queued job keep their sentinels until the queue is
+    flushed (by that last job for the ones before it, by nnhipWeightGradFlush for the last one), and every output is then
+    BIT-identical to the same calls outside the window."""
+    import torch
+    from neunet_hip._lib import call_hip_function, get_current_stream_ptr
+    rng = np.random.default_rng(62)
+    st = get_current_stream_ptr()
+    # (norm, rows, cols, dW, dB)
+    specs = [("rms", 64, 4096, True, False), ("ln", 300, 512, True, True), ("rms", 300, 512, True, True),
+             ("ln", 777, 512, True, False), ("ln", 64, 512, False, False), ("ln", 33, 1000, True, True), ("ln", 33, 1001, True, True)]
+    jobs = []
+    for norm, rows, cols, want_w, want_b in specs:
+        X, dY = dev(rng.standard_normal((rows, cols)) * 1.3 + 0.2), dev(rng.standard_normal((rows, cols)))
+        w = dev(rng.uniform(0.5, 1.5, cols))
+        if norm == "rms":
+            stats = (torch.sqrt((X * X).mean(dim=1) + 1e-6).contiguous(), None)
+        else:
+            stats = (X.mean(dim=1).contiguous(), (1.0 / torch.sqrt(X.var(dim=1, unbiased=False) + 1e-5)).contiguous())
+        jobs.append((X, dY, w, stats))
+
+    def sentinels_intact(outs):
+        torch.cuda.synchronize()
+        return all(bool((o == s).all()) for _, dw, db in outs for o, s in ((dw, 123.0), (db, 321.0)))
+
+    def submit(outs, defer):
+        for (norm, rows, cols, want_w, want_b), (X, dY, w, stats) in zip(specs, jobs):
+            if defer and len(outs) == len(specs) - 1:
+                assert sentinels_intact(outs[1:]), "a deferred column sum ran before the queue was flushed"
+            dx = torch.full_like(X, float("nan"))
+            dw, db = torch.full((cols,), 123.0, device="cuda"), torch.full((cols,), 321.0, device="cuda")
+            pw, pb = dw if want_w else None, db if want_b else None
+            if norm == "rms":
+                call_hip_function("nnhipRMSNormBackward", dY, X, w, stats[0], None, dx, pw, pb, rows, cols, st)
+            else:
+                call_hip_function("nnhipLayerNormBackward", dY, X, w, stats[0], stats[1], dx, pw, pb, rows, cols, st)
+            outs.append((dx, dw, db))
+        if defer:
+            assert sentinels_intact(outs[-1:]), "a deferred column sum ran before the flush"
+            assert not any(bool(torch.isnan(dx).any()) for dx, _, _ in outs), "dX must not wait for the flush"
+
+    def run(defer):
+        outs = []
+        if defer:
+            call_hip_function("nnhipWeightGradDefer", 1, st)
+        try:
+            submit(outs, defer)
+        finally:                              # a failed assertion must not leave the window open for the tests that follow
+            if defer:
+                call_hip_function("nnhipWeightGradFlush", st)
+                call_hip_function("nnhipWeightGradDefer", 0, st)
+            torch.cuda.synchronize()
+        return outs
+
+    a, b = run(True), run(False)
+    for (dxa, dwa, dba), (dxb, dwb, dbb), (norm, rows, cols, want_w, want_b), (X, dY, w, stats) in zip(a, b, specs, jobs):
+        assert torch.equal(dxa, dxb) and torch.equal(dwa, dwb) and torch.equal(dba, dbb), (norm, rows, cols)
+        assert bool((dwa == 123.0).all()) != want_w and bool((dba == 321.0).all()) != want_b, (norm, rows, cols)
+        if norm == "ln":
+            dXr, dwr, dbr = layernorm_backward(layernorm_forward(host(X), host(w))[1], host(dY))
+            assert_close_scaled(host(dxa), dXr, err_msg="dX")
+            if want_w:
+                assert_close_scaled(host(dwa), dwr, err_msg="dw")
+            if want_b:
+                assert_close_scaled(host(dba), dbr, err_msg="db")
+
+
 # ------------------------------------------------------------------------------------------- the decode kernel
 def decode_case(seed, B, H, dh, Tmax, lengths):
     """Random q|k|v rows and a cache whose rows hold lengths[b] live tokens; everything past the live length is NaN."""
