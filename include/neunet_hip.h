@@ -463,6 +463,43 @@ int nnhipConv2dForward(const float* X, const float* W, const float* bias, float*
 int nnhipConv2dBackward(const float* X, const float* W, const float* dO, float* dX, float* dW,
                         float* db, const nnhipConv2dDesc* d, nnhipStream_t stream);
 
+/* ---- ConvTranspose2d  (net-new exports, ABI 216; reference CPU: neunet/nn/layers/convtranspose2d.py:249-262, 293-384, 16-120)
+ *   X [B,Cin,H,W], W [Cout,Cin,kh,kw] (the reference's layout, NOT torch's [in,out,kh,kw]), bias [Cout] or NULL, O [B,Cout,Ho,Wo].
+ *   O[b,o,y,x] = bias[o] + sum_{i,k,l} W[o,i,k,l] X[b,i,h,w]  with  h sh = y + pu - (kh-1-k) dh,  w sw = x + pl - (kw-1-l) dw
+ *   (terms with exact divisions and 0 <= h < H, 0 <= w < W);  Ho = (H-1) sh - (pu+pd) + dh (kh-1) + oph + 1, likewise Wo.
+ *   = torch conv_transpose2d(X, W.flip(2,3).transpose(0,1), bias, stride, padding, output_padding, dilation) for symmetric padding;
+ *   pd / pr and the output padding only change Ho / Wo.  Padding beyond d (k-1) and strides beyond the kernel are accepted;
+ *   output padding must stay below max(stride, dilation) per axis (NNHIP_EINVAL otherwise).  Status rules as nnhipConv2d*:
+ *   bad descriptor / empty output / a tensor of 2 GiB or more / null required pointer: NNHIP_EINVAL; B == 0: NNHIP_OK, nothing
+ *   launched; 4-byte alignment suffices.  Deterministic; dW / db are written, not accumulated. */
+typedef struct nnhipConvTranspose2dDesc {
+    int64_t B, Cin, H, W, Cout, kh, kw;
+    int64_t sh, sw, dh, dw;
+    int64_t pu, pd, pl, pr;
+    int64_t oph, opw;
+} nnhipConvTranspose2dDesc;
+int nnhipConvTranspose2dForward(const float* X, const float* W, const float* bias, float* O,
+                                const nnhipConvTranspose2dDesc* d, nnhipStream_t stream);
+/* dX/dW/db may be NULL (skipped). */
+int nnhipConvTranspose2dBackward(const float* X, const float* W, const float* dO, float* dX, float* dW, float* db,
+                                 const nnhipConvTranspose2dDesc* d, nnhipStream_t stream);
+/* How a forward runs.  Stride 1 with pu <= dh (kh-1), pl <= dw (kw-1) always goes to nnhipConv2d* (CONV2D: it is a Conv2d of the
+ * same weight; so do its three gradients).  Otherwise PHASE = one dense implicit GEMM per stride phase over exactly the taps that
+ * reach it, GATHER = the Conv2d input-gradient kernel, which walks every tap for every output pixel (handles everything).
+ * AUTO: PHASE where every phase has at least one tap, GATHER otherwise.  A request for PHASE falls to GATHER at stride 1 and
+ * above 65535 phases.  The setter returns the previous value (an unknown route changes nothing); process-wide. */
+#define NNHIP_CONVT_ROUTE_AUTO 0
+#define NNHIP_CONVT_ROUTE_PHASE 1
+#define NNHIP_CONVT_ROUTE_GATHER 2
+#define NNHIP_CONVT_ROUTE_CONV2D 3   /* reported by nnhipConvTranspose2dPlan only */
+int nnhipSetConvTransposeRoute(int route);
+int nnhipGetConvTransposeRoute(void);
+/* Host only, no device work: the plan the forward would use.  Returns the number of stride phases (sh*sw) and fills, per phase
+ * (row-major in (py, px) = ((y+pu) mod sh, (x+pl) mod sw)), the number of taps that reach it and the number of output pixels per
+ * image in it; *route = the route AUTO resolves to.  capacity < phases (or a bad descriptor / null pointer): NNHIP_EINVAL. */
+int nnhipConvTranspose2dPlan(const nnhipConvTranspose2dDesc* d, int32_t* route, int32_t* phase_taps, int32_t* phase_pixels,
+                             int32_t capacity);
+
 /* ---- Embedding (reference CPU: neunet/nn/layers/embedding.py:61-75 via
  *      Tensor.__getitem__, neunet/autograd.py:895-916) ------------------------------------------------
  * out[p,:] = weight[ids[p],:] * scale + (pe ? pe[p % seq_len,:] : 0);  ids int32 (negative = from the end).

@@ -17,4 +17,14 @@ int conv_mfma_forward(const float* X, const float* W, const float* bias, float* 
 int conv_mfma_dgrad(const float* dO, const float* W, float* dX, const ConvGeom& g, hipStream_t st);
 int conv_mfma_wgrad(const float* X, const float* dO, float* dW, float* db, const ConvGeom& g, hipStream_t st);
 
+// ConvTranspose2d (conv_transpose.hip) on the same kernels.  `g` is the MIRRORED Conv2d geometry -- the Conv2d whose input gradient
+// is the transposed convolution's forward: g.Cin / g.H / g.W are the layer's OUTPUT channels and size, g.Cout / g.Ho / g.Wo its
+// input's -- and Wt the layer's weight [out][in][kh][kw] (= [g.Cin][g.Cout][taps], taps reversed; conv_repack's tconv mode).
+//   tconv_gather : O  = the dgrad gather of (X, Wt) + bias   (every tap for every output pixel)
+//   tconv_dgrad  : dX = the strided Conv2d forward of dO
+int conv_mfma_tconv_gather(const float* X, const float* Wt, const float* bias, float* O, const ConvGeom& g, hipStream_t st);
+int conv_mfma_tconv_dgrad(const float* dO, const float* Wt, float* dX, const ConvGeom& g, hipStream_t st);
+// Wr[tap][Mp][Csp] (zero padded, k-major) from a weight: the operand of the tap-outermost kernels
+int conv_repack(const float* W, float* Wr, const ConvGeom& g, int Mp, int Csp, bool dgrad, bool tconv, hipStream_t st);
+
 }  // namespace nnhip

@@ -137,6 +137,84 @@ class linear_gemv:
         return False
 
 
+class conv_transpose_route:
+    """`with neunet_hip.conv_transpose_route("phase" | "gather" | "auto"):` -- how ConvTranspose2d forwards with a stride above 1
+    run for the duration of a block (nnhipSetConvTransposeRoute; process-wide): the stride-phase kernel, the Conv2d
+    input-gradient gather, or the library's own choice.  The previous route comes back on exit, exceptions included."""
+
+    def __init__(self, route="auto"):
+        from .nn.experimental.conv_transpose2d import ROUTES
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {sorted(ROUTES)} (got {route!r})")
+        self.route = ROUTES[route]
+
+    def __enter__(self):
+        from ._lib import call_hip_function
+        self.previous = call_hip_function("nnhipSetConvTransposeRoute", self.route)
+        return self
+
+    def __exit__(self, *exc):
+        from ._lib import call_hip_function
+        call_hip_function("nnhipSetConvTransposeRoute", self.previous)
+        return False
+
+
+def concatenate(*tensors, axis=1):
+    """neunet.concatenate (neunet/__init__.py): the U-Net's skip connections.  Plumbing: the copy is torch.cat (np.concatenate on the
+    host), the gradient is handed back as `narrow` views of the output's."""
+    if not tensors or not all(isinstance(t, Tensor) for t in tensors):
+        raise TypeError("concatenate takes Tensors")
+    device = tensors[0].device
+    if any(t.device != device for t in tensors):
+        raise ValueError("Tensors must be on the same device")
+    ax = axis + tensors[0].ndim if axis < 0 else axis
+    sizes = [t.shape[ax] for t in tensors]
+    if device == "cpu":
+        data = np.concatenate([t.data for t in tensors], axis=ax)
+    else:
+        import torch
+        data = torch.cat([t.data for t in tensors], dim=ax)
+    rg = any(t.requires_grad for t in tensors)
+    out = Tensor(data, tensors if rg else None, "concatenate", requires_grad=rg, device=device, _nocopy=True)
+
+    def grad_fn(*args, grad):
+        start = 0
+        for t, n in zip(args, sizes):
+            if t.requires_grad:
+                if isinstance(grad, np.ndarray):
+                    t.apply_grad(np.take(grad, range(start, start + n), axis=ax))
+                else:
+                    t.apply_grad(grad.narrow(ax, start, n).contiguous())
+            start += n
+
+    out.grad_fn = grad_fn
+    return out
+
+
+def add_channel_bias(h: Tensor, t: Tensor) -> Tensor:
+    """h [B, C, H, W] + t [B, C][:, :, None, None] -- the U-Net's time embedding joining a feature map (the reference writes it as a
+    broadcasting Tensor add, examples/ddpm.ipynb cell 5).  dh = grad, dt = grad summed over H and W.  Plumbing (a broadcast add
+    and a sum); Tensor.add keeps refusing broadcasts."""
+    if not isinstance(h, Tensor) or not isinstance(t, Tensor):
+        raise TypeError("add_channel_bias takes Tensors")
+    if h.device != t.device:
+        raise ValueError("Tensors must be on the same device")
+    if h.ndim != 4 or tuple(t.shape) != tuple(h.shape[:2]):
+        raise ValueError(f"add_channel_bias needs h [B, C, H, W] and t [B, C] (got {h.shape} and {t.shape})")
+    rg = h.requires_grad or t.requires_grad
+    out = Tensor(h.data + t.data[:, :, None, None], (h, t) if rg else None, "add_channel_bias", requires_grad=rg, device=h.device,
+                 _nocopy=True)
+
+    def grad_fn(a, b, grad):
+        if a.requires_grad:
+            a.apply_grad(grad)
+        if b.requires_grad:
+            b.apply_grad(grad.sum(axis=(2, 3)) if isinstance(grad, np.ndarray) else grad.sum(dim=(2, 3)))
+
+    out.grad_fn = grad_fn
+    return out
+
+
 def save(obj, path):
     """neunet.save = pickle (neunet/__init__.py:26-29)."""
     import pickle

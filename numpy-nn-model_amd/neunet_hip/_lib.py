@@ -28,6 +28,12 @@ class Conv2dDesc(ctypes.Structure):
                                        "pu", "pd", "pl", "pr")]
 
 
+class ConvTranspose2dDesc(ctypes.Structure):
+    """struct nnhipConvTranspose2dDesc (include/neunet_hip.h)."""
+    _fields_ = [(n, c_int64) for n in ("B", "Cin", "H", "W", "Cout", "kh", "kw", "sh", "sw", "dh", "dw",
+                                       "pu", "pd", "pl", "pr", "oph", "opw")]
+
+
 class AttentionOptions(ctypes.Structure):
     """struct nnhipAttentionOptions (include/neunet_hip.h)."""
     _fields_ = [("mask_bits", c_void_p), ("mask_bitsT", c_void_p), ("row_any", c_void_p), ("dropout_mask", c_void_p),
@@ -151,6 +157,11 @@ _SIGNATURES = {
     "nnhipFusedOptimizerSetGradDivisor": (ctypes.c_int, [c_void_p, P]),
     "nnhipConv2dForward": (ctypes.c_int, [P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConv2dBackward": (ctypes.c_int, [P, P, P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
+    "nnhipConvTranspose2dForward": (ctypes.c_int, [P, P, P, P, POINTER(ConvTranspose2dDesc), c_void_p]),
+    "nnhipConvTranspose2dBackward": (ctypes.c_int, [P, P, P, P, P, P, POINTER(ConvTranspose2dDesc), c_void_p]),
+    "nnhipSetConvTransposeRoute": (ctypes.c_int, [ctypes.c_int]),
+    "nnhipGetConvTransposeRoute": (ctypes.c_int, []),
+    "nnhipConvTranspose2dPlan": (ctypes.c_int, [POINTER(ConvTranspose2dDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_int32]),
     "nnhipLSTMForward": (ctypes.c_int, [P, POINTER(LSTMWeights), P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64,
                                         ctypes.c_int, ctypes.c_int, c_void_p]),
     "nnhipLSTMBackward": (ctypes.c_int, [P, POINTER(LSTMWeights), P, P, P, P, P, P, POINTER(LSTMGrads), c_int64, c_int64, c_int64,
@@ -189,7 +200,8 @@ _SIGNATURES = {
     "nnhipBroadcastF32": (ctypes.c_int, [c_void_p, P, c_int64, ctypes.c_int, c_void_p]),
 }
 _NO_STATUS = {"nnhipVersion", "nnhipLinearReLULinearBackwardFits", "nnhipBatchNorm2dLinearSigmoidMSEFits", "nnhipConv2dLeakyMaxPoolStatsBlocks", "nnhipGetLastErrorString", "nnhipCreateFusedOptimizer", "nnhipGetGemmMode", "nnhipGetGemmLockstep", "nnhipConv2dWeightGradPooledOk", "nnhipConv2dLeakyMaxPoolForwardOk", "nnhipGemmLaunchCount",
-              "nnhipWeightGradPending", "nnhipGetLinearGemv"}
+              "nnhipWeightGradPending", "nnhipGetLinearGemv", "nnhipSetConvTransposeRoute", "nnhipGetConvTransposeRoute",
+              "nnhipConvTranspose2dPlan"}
 
 _dll = None
 _funcs: dict = {}

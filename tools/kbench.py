@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "numpy-nn-model_amd"))
 import torch  # noqa: E402
 
 from neunet_hip import _lib  # noqa: E402
-from neunet_hip._lib import Conv2dDesc, call_hip_function as call  # noqa: E402
+from neunet_hip._lib import Conv2dDesc, ConvTranspose2dDesc, call_hip_function as call  # noqa: E402
 import ctypes  # noqa: E402
 
 
@@ -334,6 +334,44 @@ def main():
             report(f"conv fwd      {B}x{Cin}x{H}x{H}->{Cout}", *bench(lambda: call("nnhipConv2dForward", X, W, bb, O_, ctypes.byref(d), st), args.iters), flops=fl)
             report(f"conv dgrad    {B}x{Cin}x{H}x{H}->{Cout}", *bench(lambda: call("nnhipConv2dBackward", X, W, dO, dX, None, None, ctypes.byref(d), st), args.iters), flops=fl)
             report(f"conv wgrad+db {B}x{Cin}x{H}x{H}->{Cout}", *bench(lambda: call("nnhipConv2dBackward", X, W, dO, None, dW, db, ctypes.byref(d), st), args.iters), flops=fl)
+
+    if "convt" in only:
+        # the up-block transforms of the reference's DDPM U-Net (examples/ddpm.ipynb cell 5: ConvTranspose2d(C, C, 4x4, stride 2,
+        # padding 1)) at the batch convu uses: the UTKFace configuration's three, then the MNIST configuration's two.  The forward
+        # on the stride-phase kernel and on the dgrad gather ALTERNATE in this process (`rounds` rounds each; the spread is
+        # (max - min) / median of a route's round medians); their outputs are compared on the seeded inputs first.
+        # FLOP/s on the algorithmic count 2 B H W Cin Cout kh kw.
+        rounds = 5
+        for (B, C, H) in [(64, 512, 4), (64, 256, 8), (64, 128, 16), (64, 64, 8), (64, 32, 16)]:
+            X, W, bb = rnd(B, C, H, H), rnd(C, C, 4, 4) / (4 * C ** 0.5), rnd(C)
+            O_, dO = torch.empty(B, C, 2 * H, 2 * H, device=dev), rnd(B, C, 2 * H, 2 * H)
+            dX, dW, db = torch.empty_like(X), torch.empty_like(W), torch.empty_like(bb)
+            d = ConvTranspose2dDesc(B, C, H, H, C, 4, 4, 2, 2, 1, 1, 1, 1, 1, 1, 0, 0)
+            fl = 2.0 * B * H * H * C * C * 16
+            tag = f"{B}x{C}x{H}x{H}->{2 * H}x{2 * H}"
+            fwd = lambda: call("nnhipConvTranspose2dForward", X, W, bb, O_, ctypes.byref(d), st)  # noqa: E731
+            outs = {}
+            for route in (1, 2):
+                prev = call("nnhipSetConvTransposeRoute", route)
+                fwd()
+                outs[route] = O_.clone()
+                call("nnhipSetConvTransposeRoute", prev)
+            diff = float((outs[1] - outs[2]).abs().max())
+            ref = torch.nn.functional.conv_transpose2d(X.double(), W.double().flip(2, 3).transpose(0, 1), bb.double(), 2, 1)
+            err = [float((outs[r].double() - ref).abs().max()) for r in (1, 2)]
+            print(f"convT {tag}: |phase - gather| max {diff:.2e}; vs float64 phase {err[0]:.2e} gather {err[1]:.2e} (|O| max {float(ref.abs().max()):.2f})")
+            meds = {1: [], 2: []}
+            for _ in range(rounds):
+                for route in (1, 2):
+                    prev = call("nnhipSetConvTransposeRoute", route)
+                    meds[route].append(bench(fwd, args.iters)[0])
+                    call("nnhipSetConvTransposeRoute", prev)
+            for route, name in ((1, "phase "), (2, "gather")):
+                m = np.array(meds[route])
+                report(f"convT fwd {name} {tag}", float(np.median(m)), float(m.min()), flops=fl)
+                print(f"{'':34s} round medians {' '.join(f'{v:.4f}' for v in m)}  spread {(m.max() - m.min()) / np.median(m) * 100:.1f} %")
+            report(f"convT dX         {tag}", *bench(lambda: call("nnhipConvTranspose2dBackward", X, W, dO, dX, None, None, ctypes.byref(d), st), args.iters), flops=fl)
+            report(f"convT dW+db      {tag}", *bench(lambda: call("nnhipConvTranspose2dBackward", X, W, dO, None, dW, db, ctypes.byref(d), st), args.iters), flops=fl)
 
     if want("conv"):
         for (B, Cin, H, Cout) in [(256, 1, 28, 8), (256, 8, 14, 16)]:
