@@ -755,6 +755,28 @@ int nnhipKVCacheFill(const float* qkv, float* Kcache, float* Vcache, const int32
 int nnhipSampleTopK(int32_t* out_ids, float* u_out, const float* logits, int64_t rows, int64_t n, int64_t ld, int32_t top_k,
                     float temperature, uint32_t seed, const uint32_t* seed_dev, nnhipStream_t stream);
 
+/* ---- seq2seq inference (net-new exports, ABI 217; csrc/attention_cross_decode.hip) -------------------------------------------------
+ * The cross-attention of ONE new decoder row against a read-only encoder memory: what a cached step of the reference's predict()
+ * loop (examples/seq2seq.ipynb cell 17, which re-runs the whole decoder per token) needs from DecoderLayer.cross_attn (cell 5) and
+ * MultiHeadAttention.forward (cell 2), with the attention map of cell 21's plot.
+ *   Q          [B, D], D = H * head_dim, row stride ld_q floats (it may be a column block of a wider buffer)
+ *   Kmem, Vmem [B, H, S, head_dim] each, HEAD-MAJOR (the KVCache layout with Tmax = S); only read
+ *   key_valid  NULL, or int32 [B, S]: 0 = padding (holes allowed)
+ *   O          [B, D] dense;   P  NULL, or [B, H, S]: receives the softmax probabilities (cell 2's `attn` for this query row)
+ * s_j = (key_valid && !key_valid[b*S+j]) ? -1e9 : scale * q.k_j and O = softmax(s) V -- the rule of nnhipMaskedSoftmaxForward: a masked
+ * key is -1e9, not -inf, so a fully masked row is the plain average of all S values.  One launch, no workspace, no atomics; fixed
+ * reduction orders: bit-identical from run to run, and O has the same bits with and without P.  One block per (b, h) walks all S
+ * keys -- there is no key split, so a long memory with a small B*H is slow by construction.
+ * Checked on the host before any launch.  NNHIP_EINVAL: a NULL Q / Kmem / Vmem / O, head_dim outside {32, 64, 128}, S < 1 with
+ * B > 0, ld_q < D or ld_q % 4 != 0.  NNHIP_EALIGN: Q, Kmem, Vmem or O not 16-byte aligned.  B == 0: returns 0, launches nothing. */
+int nnhipAttentionDecodeCross(const float* Q, const float* Kmem, const float* Vmem, const int32_t* key_valid, float* O, float* P,
+                              int64_t B, int64_t H, int64_t S, int64_t head_dim, int64_t ld_q, float scale, nnhipStream_t stream);
+/* Fills such a memory once per source sentence (cell 17 encodes once): token-major projections K, V [B, S, D] with one common row
+ * stride ld floats (2D for the two column blocks of a fused K|V projection) -> Kmem, Vmem [B, H, S, head_dim], one launch.  The
+ * same status rules (ld in place of ld_q; K, V, Kmem, Vmem in place of the four operands). */
+int nnhipKVMemoryFill(const float* K, const float* V, float* Kmem, float* Vmem, int64_t B, int64_t H, int64_t S, int64_t head_dim,
+                      int64_t ld, nnhipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,8 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "comm.hip", "recurrent.hip", "sample.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"),
+SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "sample.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
 
@@ -39,6 +39,8 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             # the KV-cached decode kernel keeps U x (K, V) float4 loads in flight per lane (64 registers at head dim 128): HBM-bound,
             # a spill would put the in-flight loads' destinations in scratch
             "attention_decode.hip": (r"attn_decode_kernel", r"attn_decode_merge_kernel"),
+            # the same lane layout against a read-only encoder memory (plus the fill copy): the same reason
+            "attention_cross_decode.hip": (r"attn_cross_decode_kernel", r"kv_memory_fill_kernel"),
             # the sampler's first kernel holds its chunk (8 x 64-bit order keys per lane) in registers across the radix-select passes
             "sample.hip": (r"sample_chunk_topk_kernel", r"sample_draw_kernel"),
             # the 1..8-row Linear forward keeps NR x U float4 weight loads in flight per lane next to NR x rows accumulators: a spill

@@ -26,12 +26,9 @@
 // key from the qkv row, not from the cache, so no block reads what another one writes in the same launch.  cache_len is
 // a device int32[B] that this kernel only reads (rows of a batch may differ; the host advances it with its own op).
 // A row with cache_len[b] outside 0 .. Tmax-1 raises the device error word and is skipped: nothing of that row is written.
-#include "common.h"
+#include "attention_decode.h"      // the lane layout, shared with attention_cross_decode.hip
 
 namespace nnhip {
-
-constexpr int DEC_THREADS = 256, DEC_WAVES = 4, DEC_U = 4, DEC_PASS = 64;
-typedef float dec_f4 __attribute__((ext_vector_type(4)));
 
 struct DecodePlan { int splits; int chunk; };
 // chunk: a multiple of DEC_PASS keys; splits * chunk >= Tmax.  Asks for 1024 blocks (4 per CU of a 256-CU part) and gets fewer
@@ -51,24 +48,13 @@ static DecodePlan decode_plan(int64_t B, int64_t H, int64_t Tmax) {
     return DecodePlan{(int)ceil_div(Tmax, chunk), (int)chunk};
 }
 
-template <int LPK>
-__device__ __forceinline__ float group_sum(float v) {      // sum over the LPK adjacent lanes that own one key
-    v += dpp_f32<kDppXor1>(v);
-    v += dpp_f32<kDppXor2>(v);
-    v += dpp_f32<kDppHalfMirror>(v);
-    if constexpr (LPK == 16) v += dpp_f32<kDppMirror>(v);
-    return v;
-}
-
 // grid (splits, B*H), 256 threads.  part: [B*H][splits][DH + 2] = (m, l, o[DH]), m in the log2 domain.
 template <int DH>
 __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(
     const float* __restrict__ qkv, float* __restrict__ Kc, float* __restrict__ Vc, const int32_t* __restrict__ cache_len,
     float* __restrict__ O, float* __restrict__ part, int H, int Tmax, int64_t ld, float scale_log2e, int chunk, unsigned* err) {
-    constexpr int LPK = DH / 4 < 16 ? DH / 4 : 16;       // lanes per key
-    constexpr int NV = DH / (4 * LPK);                   // float4 per lane and key (2 for dh 128)
-    constexpr int KPW = 64 / LPK;                        // keys per wave-load
-    constexpr int NSLOT = DEC_WAVES * KPW;
+    using L = DecLanes<DH>;
+    constexpr int LPK = L::LPK, NV = L::NV, KPW = L::KPW, NSLOT = L::NSLOT;
     __shared__ float s_m[NSLOT], s_l[NSLOT];
     __shared__ __attribute__((aligned(16))) float s_o[NSLOT][DH + 4];
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
@@ -124,18 +110,8 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(
         }
 #pragma unroll
         for (int u = 0; u < DEC_U; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) d += (q[v].x * kk[u][v].x + q[v].y * kk[u][v].y) + (q[v].z * kk[u][v].z + q[v].w * kk[u][v].w);
-            d = group_sum<LPK>(d);                                    // wave-converged: every lane takes part, live key or not
-            const float sc = ok[u] ? d : -INFINITY;
-            const float mn = fmaxf(m, sc);
-            const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m - mn);
-            const float p = ok[u] ? __builtin_amdgcn_exp2f(sc - mn) : 0.f;
-            l = l * alpha + p;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) o[v] = o[v] * alpha + vv[u][v] * p;
-            m = mn;
+            const float d = group_sum<LPK>(dec_dot<NV>(q, kk[u]));     // wave-converged: every lane takes part, live key or not
+            dec_online_step<NV>(ok[u] ? d : -INFINITY, ok[u], vv[u], m, l, o);
         }
     }
     // ---- the block's NSLOT states -> one (m, l, o[DH]), folded in slot order ----------------------------------------

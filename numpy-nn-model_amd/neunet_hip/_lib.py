@@ -146,6 +146,8 @@ _SIGNATURES = {
     "nnhipAttentionDecodeWorkspace": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     "nnhipAttentionDecode": (ctypes.c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p]),
     "nnhipKVCacheFill": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipAttentionDecodeCross": (ctypes.c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p]),
+    "nnhipKVMemoryFill": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipFusedAdamWStep": (ctypes.c_int, [P, P, P, P, c_double, c_double, c_double, c_double, c_double, c_int32, c_int64, c_int32, c_float, c_void_p]),
     "nnhipCreateFusedOptimizer": (c_void_p, []),
     "nnhipDestroyFusedOptimizer": (ctypes.c_int, [c_void_p]),

@@ -10,7 +10,7 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPPositionalEncoding as PositionalEncoding, HIPBatchNorm2d as BatchNorm2d,
                            HIPLeakyReLU as LeakyReLU, HIPMaxPool2d as MaxPool2d, HIPMSELoss as MSELoss,
                            HIPSigmoid as Sigmoid, HIPLSTM as LSTM, HIPLayerNorm as LayerNorm, HIPGELU as GELU,
-                           HIPCausalSelfAttention as CausalSelfAttention, KVCache,
+                           HIPCausalSelfAttention as CausalSelfAttention, KVCache, CrossAttentionMemory,
                            HIPConvTranspose2d as ConvTranspose2d)
 
 

@@ -8,7 +8,7 @@ from .losses import CUDACrossEntropyLoss, HIPCrossEntropyLoss  # noqa: F401
 from .rmsnorm import CUDARMSNorm, HIPRMSNorm  # noqa: F401
 from .conv2d import HIPConv2d  # noqa: F401
 from .conv_transpose2d import HIPConvTranspose2d  # noqa: F401
-from .attention import HIPMultiHeadAttention  # noqa: F401
+from .attention import CrossAttentionMemory, HIPMultiHeadAttention  # noqa: F401
 from .embedding import HIPDropout, HIPEmbedding, HIPPositionalEncoding  # noqa: F401
 from .vision import HIPBatchNorm2d, HIPLeakyReLU, HIPMaxPool2d, HIPMSELoss, HIPSigmoid  # noqa: F401
 from .recurrent import HIPLSTM  # noqa: F401

@@ -234,7 +234,7 @@ class _HIPQKVProjTensor(Tensor):
             import torch
             grad = grad if grad.is_contiguous() else grad.contiguous()
             gW = _fused_grad_dest(weights, (3 * D, D))
-            gb = _fused_grad_dest(biases, (3, D))
+            gb = _fused_grad_dest(biases, (3, D)) if biases is not None else None      # bias=False: no db at all
             grad_X = torch.empty_like(X.data) if X.requires_grad else None
             held = X.foldable_grad() if grad_X is not None else None
             hook = getattr(weights[0], "_grad_hook", None)
@@ -242,9 +242,10 @@ class _HIPQKVProjTensor(Tensor):
                 hip_linear_module_backward(X.data, Wqkv, grad, None, gW, gb, rows, D, 3 * D)
             else:
                 hip_linear_module_backward(X.data, Wqkv, grad, grad_X, gW, gb, rows, D, 3 * D, grad_X_addend=held)
-            for i, (w, b) in enumerate(zip(weights, biases)):
+            for i, w in enumerate(weights):
                 _finish_param(w, gW[i * D:(i + 1) * D])
-                _finish_param(b, gb[i:i + 1])
+                if biases is not None:
+                    _finish_param(biases[i], gb[i:i + 1])
             if hook is not None and grad_X is not None:
                 hip_linear_module_backward(X.data, Wqkv, grad, grad_X, None, None, rows, D, 3 * D, grad_X_addend=held)
             if grad_X is not None:
@@ -295,7 +296,8 @@ class _HIPFusedSelfAttentionTensor(Tensor):
 
 
 class HIPMultiHeadAttention(Module):
-    def __init__(self, d_model, n_heads, dropout=0.0, device="cuda"):
+    def __init__(self, d_model, n_heads, dropout=0.0, bias=True, device="cuda"):
+        """bias=False: wq, wk, wv without bias and fc with one -- the block of examples/seq2seq.ipynb cell 2 (gpt.ipynb's has all four)."""
         super().__init__()
         if d_model % n_heads != 0:
             raise ValueError("d_model must be divisible by n_heads")
@@ -303,9 +305,9 @@ class HIPMultiHeadAttention(Module):
         self.scale = math.sqrt(d_model)  # the notebook divides by sqrt(d_model), not sqrt(depth)
         self.dropout = HIPDropout(dropout)
         self.depth = d_model // n_heads
-        self.wq = HIPLinear(d_model, d_model, device=device)
-        self.wk = HIPLinear(d_model, d_model, device=device)
-        self.wv = HIPLinear(d_model, d_model, device=device)
+        self.wq = HIPLinear(d_model, d_model, bias=bias, device=device)
+        self.wk = HIPLinear(d_model, d_model, bias=bias, device=device)
+        self.wv = HIPLinear(d_model, d_model, bias=bias, device=device)
         self.fc = HIPLinear(d_model, d_model, device=device)
         self.fuse_qkv = True     # self-attention + need_weights=False + a fused head dim: one GEMM for the q|k|v projections
         self.dropout_seed_dev = None     # optional device int32 tensor added to the dropout seed inside the kernels (set it to
@@ -322,19 +324,24 @@ class HIPMultiHeadAttention(Module):
         import torch
         D = self.d_model
         lins = (self.wq, self.wk, self.wv)
-        ws, bs = [lin.weight for lin in lins], [lin.bias for lin in lins]
+        ws = [lin.weight for lin in lins]
+        bs = [lin.bias for lin in lins] if self.wq.bias is not None else None
         if not _adjacent([w.data for w in ws]):
             buf = torch.empty((3 * D, D), dtype=torch.float32, device=ws[0].data.device)
             for i, w in enumerate(ws):
                 buf[i * D:(i + 1) * D].copy_(w.data)
                 w.data = buf[i * D:(i + 1) * D]
+        Wqkv = torch.as_strided(ws[0].data, (3 * D, D), (D, 1))
+        ws[0]._bucket_group = ws                                # GradBucket keeps their slots back-to-back
+        if bs is None:
+            return ws, None, Wqkv, None
         if not _adjacent([b.data for b in bs]):
             buf = torch.empty((3, D), dtype=torch.float32, device=bs[0].data.device)
             for i, b in enumerate(bs):
                 buf[i:i + 1].copy_(b.data.reshape(1, D))
                 b.data = buf[i:i + 1]
-        ws[0]._bucket_group, bs[0]._bucket_group = ws, bs      # GradBucket keeps their slots back-to-back
-        return ws, bs, torch.as_strided(ws[0].data, (3 * D, D), (D, 1)), torch.as_strided(bs[0].data, (1, 3 * D), (3 * D, 1))
+        bs[0]._bucket_group = bs
+        return ws, bs, Wqkv, torch.as_strided(bs[0].data, (1, 3 * D), (3 * D, 1))
 
     def _forward_fused_qkv(self, x: Tensor, key_valid, causal, residual, opts):
         import torch
@@ -385,8 +392,7 @@ class HIPMultiHeadAttention(Module):
         fusable = not need_weights and self.depth in FUSED_HEAD_DIMS
         if fusable:
             opts = self._fused_options(mask, drop_mask, dropping)
-            if (q is k and k is v and self.fuse_qkv and self.wq.bias is not None and q.dtype == "float32"
-                    and q.data.is_contiguous()):
+            if q is k and k is v and self.fuse_qkv and q.dtype == "float32" and q.data.is_contiguous():
                 return self._forward_fused_qkv(q, key_valid, causal, residual, opts), None
             qp, kp, vp = self.wq(q), self.wk(k), self.wv(v)
             ctx, lse = fused_attention_forward(qp.data, kp.data, vp.data, key_valid, self.n_heads, self.scale, causal, opts)
@@ -416,3 +422,113 @@ class HIPMultiHeadAttention(Module):
         ctx_t = _HIPAttentionTensor(ctx, (qp, kp, vp, attn, key_valid, self.n_heads, self.scale, causal, drop_mask,
                                           used if drop_mask is not None else None, dense), "attention", device="cuda")
         return self.fc(ctx_t, residual=residual), used
+
+    # ---- cached inference, no autograd tape (examples/seq2seq.py): a KVCacheLayer for the decoder's own prefix, a
+    # CrossAttentionMemoryLayer (below) for the encoder output
+    def fill_memory(self, enc, layer):
+        """Fill one memory layer from the encoder output enc [B, S, D]: ONE K|V GEMM over the packed [wk; wv] rows (wq, wk, wv are
+        views of one buffer), then nnhipKVMemoryFill.  No tape."""
+        import torch
+        m, D = layer.owner, self.d_model
+        xd = _no_tape_rows(enc, D)
+        if tuple(xd.shape) != (m.B, m.S, D) or (self.n_heads, self.depth) != (m.H, m.dh):
+            raise ValueError(f"memory is for (B, S, H, dh) = {(m.B, m.S, m.H, m.dh)}, got an encoder output {tuple(xd.shape)}")
+        _, _, Wqkv, bqkv = self._pack_qkv()
+        kv = torch.empty((m.B, m.S, 2 * D), dtype=torch.float32, device=xd.device)
+        hip_linear_module_forward(xd, Wqkv[D:], None if bqkv is None else bqkv[:, D:], kv, m.B * m.S, D, 2 * D)
+        call_hip_function("nnhipKVMemoryFill", StridedView(kv[..., 0:D]), StridedView(kv[..., D:]), layer.k, layer.v, m.B, m.H, m.S,
+                          m.dh, 2 * D, get_current_stream_ptr())
+
+    def self_step(self, x, cache, residual=None):
+        """One cached self-attention step: x [B, 1, D] is the new token's row; a packed q|k|v GEMM, nnhipAttentionDecode on a
+        KVCacheLayer (appends k, v at cache_len[b], attends keys 0 .. cache_len[b]), then fc with the residual in its epilogue.
+        The caller advances the KVCache after every layer of the step has run.  Returns the device array [B, 1, D].  No tape."""
+        import torch
+        from .causal_attention import attention_decode
+        c, D = cache.owner, self.d_model
+        xd = _no_tape_rows(x, D)
+        B = xd.shape[0]
+        if (B, self.n_heads, self.depth) != (c.B, c.H, c.dh) or xd.numel() != B * D:
+            raise ValueError(f"KVCache is for (B, H, dh) = {(c.B, c.H, c.dh)}; the step takes one row [B, 1, {D}] per batch row")
+        c.check_room(1)
+        _, _, Wqkv, bqkv = self._pack_qkv()
+        qkv = torch.empty((B, 3 * D), dtype=torch.float32, device=xd.device)
+        hip_linear_module_forward(xd, Wqkv, bqkv, qkv, B, D, 3 * D)
+        ctx = torch.empty((B, D), dtype=torch.float32, device=xd.device)
+        attention_decode(qkv, cache, ctx, 1.0 / self.scale)             # this block's scale: 1 / sqrt(d_model), not 1 / sqrt(head_dim)
+        return self._fc_no_tape(ctx, residual, B)
+
+    def cross_step(self, x, layer, residual=None, need_weights=False):
+        """One cached cross-attention step: the q GEMM of x [B, 1, D], nnhipAttentionDecodeCross on a filled memory layer, then fc with
+        the residual in its epilogue.  Returns (out [B, 1, D], attn): attn is None, or with need_weights=True the map [B, H, 1, S].
+        No tape."""
+        import torch
+        m, D = layer.owner, self.d_model
+        xd = _no_tape_rows(x, D)
+        B = xd.shape[0]
+        if (B, self.n_heads, self.depth) != (m.B, m.H, m.dh) or xd.numel() != B * D:
+            raise ValueError(f"memory is for (B, H, dh) = {(m.B, m.H, m.dh)}; the step takes one row [B, 1, {D}] per batch row")
+        q = torch.empty((B, D), dtype=torch.float32, device=xd.device)
+        hip_linear_module_forward(xd, self.wq.weight.data, None if self.wq.bias is None else self.wq.bias.data, q, B, D, D)
+        ctx = torch.empty((B, D), dtype=torch.float32, device=xd.device)
+        probs = torch.empty((B, m.H, m.S), dtype=torch.float32, device=xd.device) if need_weights else None
+        attention_decode_cross(q, layer, ctx, 1.0 / self.scale, probs)
+        return self._fc_no_tape(ctx, residual, B), (probs.reshape(B, m.H, 1, m.S) if need_weights else None)
+
+    def _fc_no_tape(self, ctx, residual, B):
+        import torch
+        D = self.d_model
+        out = torch.empty((B, 1, D), dtype=torch.float32, device=ctx.device)
+        addend = None if residual is None else _no_tape_rows(residual, D)
+        hip_linear_module_forward(ctx, self.fc.weight.data, self.fc.bias.data, out, B, D, D, addend=addend)
+        return out
+
+
+class CrossAttentionMemoryLayer:
+    """One decoder layer's view of a CrossAttentionMemory: what fill_memory / cross_step take."""
+    __slots__ = ("owner", "index", "k", "v")
+
+    def __init__(self, owner, index):
+        self.owner, self.index = owner, index
+        self.k, self.v = owner.k[index], owner.v[index]
+
+
+class CrossAttentionMemory:
+    """CrossAttentionMemory(B, S, n_layer, H, dh): the projected encoder output every cached decoder step attends to.  K and V are
+    [n_layer, B, H, S, dh] fp32, head-major inside a layer (KVCache's layout with Tmax = S); written once per source batch by
+    HIPMultiHeadAttention.fill_memory and only read afterwards.  key_valid: int32 device array [B, S] (0 = source padding) or None."""
+
+    def __init__(self, B, S, n_layer, H, dh, key_valid=None, device="cuda"):
+        import torch
+        if dh not in FUSED_HEAD_DIMS:
+            raise ValueError(f"CrossAttentionMemory: head dim {dh} is not one the decode kernel has ({FUSED_HEAD_DIMS})")
+        if min(B, S, n_layer, H) < 1:
+            raise ValueError("CrossAttentionMemory: B, S, n_layer and H must be >= 1")
+        if key_valid is not None and (tuple(key_valid.shape) != (B, S) or key_valid.dtype != torch.int32):
+            raise ValueError(f"CrossAttentionMemory: key_valid must be int32 [{B}, {S}]")
+        self.B, self.S, self.n_layer, self.H, self.dh = B, S, n_layer, H, dh
+        self.k = torch.zeros((n_layer, B, H, S, dh), dtype=torch.float32, device=device)
+        self.v = torch.zeros((n_layer, B, H, S, dh), dtype=torch.float32, device=device)
+        self.key_valid = key_valid.contiguous() if key_valid is not None else None
+        self._layers = [CrossAttentionMemoryLayer(self, i) for i in range(n_layer)]
+
+    def layer(self, i) -> CrossAttentionMemoryLayer:
+        return self._layers[i]
+
+
+def attention_decode_cross(q, layer: CrossAttentionMemoryLayer, out, scale, probs=None):
+    """One query row per batch row against a memory layer: q [B, D] (a column block is fine) -> out [B, D]; probs: None or
+    [B, H, S], receives the attention map (nnhipAttentionDecodeCross)."""
+    m = layer.owner
+    call_hip_function("nnhipAttentionDecodeCross", StridedView(q), layer.k, layer.v, m.key_valid, out, probs, m.B, m.H, m.S, m.dh,
+                      q.stride(0), float(scale), get_current_stream_ptr())
+    return out
+
+
+def _no_tape_rows(x, D):
+    """The device array [rows, D] of a Tensor / array [B, T, D] or [B, D] (dense)."""
+    xd = x.data if isinstance(x, Tensor) else x
+    xd = xd if xd.is_contiguous() else xd.contiguous()
+    if xd.shape[-1] != D:
+        raise ValueError(f"expected a last dimension of {D}, got {tuple(xd.shape)}")
+    return xd

@@ -835,8 +835,173 @@ def gen_ddpm():
     save("ddpm_unet", timesteps=np.int64(timesteps), **arrs)
 
 
+# --------------------------------------------------------------------------- seq2seq Transformer (examples/seq2seq.ipynb)
+SEQ2SEQ_TINY_CFG = {"vocab": 40, "d_model": 64, "n_heads": 2, "d_ff": 96, "n_layers": 2, "max_len": 64}
+SEQ2SEQ_PAD, SEQ2SEQ_SOS, SEQ2SEQ_EOS = 0, 1, 2
+SEQ2SEQ_MAX_LENGTH = 20
+SEQ2SEQ_SRC_LENGTHS = (5, 9, 13)
+# Seed of the fixture's weights: the first of 0, 1, 2, ... for which every one of the three greedy continuations meets the conditions
+# gen_seq2seq asserts, at least one of them stops at EOS and at least one runs to max_length (both arms of the stop rule); found by
+# `python tools/gen_golden.py --search-seq2seq-seed`.  Scales: an embedding of the positional table's amplitude after its * sqrt(d),
+# so that the next token depends on the position as well as on the last token, and SMALL attention / feed-forward branches -- at
+# 1/sqrt(in) and above, the input-independent part of their output (the mean of the ReLU activations, the average of the values)
+# outweighs the rest after the post-LayerNorm and the decoder repeats one token whatever it reads.
+SEQ2SEQ_TINY_SEED = 127
+SEQ2SEQ_TINY_SCALES = {"emb": 0.12, "attn": 0.5, "ffn": 0.5, "out": 1.0, "bias": 0.1}
+
+
+def _seq2seq_namespace():
+    """exec() the notebook's model cells (2-9) straight from /root/reference/examples/seq2seq.ipynb -- nothing of the notebook is
+    copied into this repository."""
+    import json
+    import math
+    from typing import Optional
+    nb = json.load(open("/root/reference/examples/seq2seq.ipynb"))
+    ns = {"nn": nn, "neunet": neunet, "Tensor": Tensor, "math": math, "np": np, "Optional": Optional, "device": "cpu"}
+    for idx in range(2, 10):
+        exec("".join(nb["cells"][idx]["source"]), ns)
+    return ns
+
+
+def _seq2seq_tiny_model(ns, seed):
+    """The notebook's model at SEQ2SEQ_TINY_CFG (dropout 0) with every parameter redrawn from `seed` at SEQ2SEQ_TINY_SCALES."""
+    c, sc = SEQ2SEQ_TINY_CFG, SEQ2SEQ_TINY_SCALES
+    kw = dict(d_model=c["d_model"], n_heads=c["n_heads"], d_ff=c["d_ff"], n_layers=c["n_layers"], dropout=0.0, max_len=c["max_len"])
+    model = ns["Seq2SeqTransformer"](encoder=ns["Encoder"](src_vocab_size=c["vocab"], **kw),
+                                     decoder=ns["Decoder"](tgt_vocab_size=c["vocab"], **kw), pad_idx=SEQ2SEQ_PAD)
+    rng = np.random.default_rng(seed)
+    sd = model.state_dict()
+    for name, value in sd.items():
+        shape = value.shape
+        if name.endswith("token_embedding.weight"):
+            new = rng.standard_normal(shape) * sc["emb"]
+        elif ".norm" in name:
+            new = rng.uniform(0.7, 1.3, shape) if name.endswith("weight") else rng.standard_normal(shape) * sc["bias"]
+        elif name.endswith("bias"):
+            new = rng.standard_normal(shape) * sc["bias"]
+        else:
+            kind = "out" if "fc_out" in name else "ffn" if ".ffn." in name else "attn"
+            new = rng.standard_normal(shape) * (sc[kind] / np.sqrt(shape[1]))
+        sd[name] = new.astype(F32)
+    model.load_state_dict(sd)
+    for k, v in model.state_dict().items():
+        np.testing.assert_array_equal(v, sd[k], err_msg=k)
+    return model
+
+
+def _seq2seq_sources(seed):
+    rng = np.random.default_rng(seed + 2000)
+    return [[SEQ2SEQ_SOS] + rng.integers(3, SEQ2SEQ_TINY_CFG["vocab"], n - 2).tolist() + [SEQ2SEQ_EOS] for n in SEQ2SEQ_SRC_LENGTHS]
+
+
+def _seq2seq_reference_greedy(model, src_ids, max_length):
+    """The token list the loop of the notebook's predict() (cell 17) builds -- the reference's own encoder / decoder / mask methods,
+    float32 -- before predict() strips SOS and EOS from it."""
+    model.eval()
+    src = np.asarray(src_ids).reshape(1, -1)
+    src_mask = model.get_pad_mask(src)
+    src, src_mask = neunet.tensor(src, dtype=neunet.int32), neunet.tensor(src_mask, dtype=neunet.int32)
+    enc_src = model.encoder.forward(src, src_mask)
+    tokens = [SEQ2SEQ_SOS]
+    for _ in range(max_length):
+        tgt = np.asarray(tokens).reshape(1, -1)
+        tgt_mask = model.get_pad_mask(tgt) & model.get_sub_mask(tgt)
+        outputs, _ = model.decoder.forward(neunet.tensor(tgt, dtype=neunet.int32), neunet.tensor(tgt_mask, dtype=neunet.int32),
+                                           enc_src, src_mask)
+        tokens.append(int(outputs.data.argmax(axis=-1)[:, -1].item()))
+        if tokens[-1] == SEQ2SEQ_EOS or len(tokens) >= max_length:
+            break
+    return tokens
+
+
+def _seq2seq_greedy_ok(tokens, logits64):
+    """(float64 picks the same tokens, the smallest top-2 margin, new tokens before EOS / max_length, distinct ids among them,
+    no PAD among them)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from seq2seq_ref import greedy_margins
+    new = [t for t in tokens[1:] if t != SEQ2SEQ_EOS]
+    same = np.array_equal(np.argmax(logits64, axis=-1), np.asarray(tokens[1:]))
+    return same, float(greedy_margins(logits64).min()), len(new), len(set(new)), SEQ2SEQ_PAD not in new
+
+
+def _seq2seq_continuations(model, seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from seq2seq_ref import teacher_forced_logits
+    params = {k: np.asarray(v) for k, v in model.state_dict().items()}
+    out = []
+    for src in _seq2seq_sources(seed):
+        tokens = _seq2seq_reference_greedy(model, src, SEQ2SEQ_MAX_LENGTH)
+        out.append((src, tokens, teacher_forced_logits(params, src, tokens, SEQ2SEQ_TINY_CFG["n_heads"], SEQ2SEQ_PAD)))
+    return out
+
+
+def _seq2seq_both_stops(new_counts):
+    """new tokens (EOS not counted) per sentence: max_length - 1 of them means the loop ran out, fewer means it met EOS."""
+    return any(n == SEQ2SEQ_MAX_LENGTH - 1 for n in new_counts) and any(n < SEQ2SEQ_MAX_LENGTH - 1 for n in new_counts)
+
+
+def search_seq2seq_seed(limit=400):
+    ns = _seq2seq_namespace()
+    for seed in range(limit):
+        seed_layers(117)
+        res = [_seq2seq_greedy_ok(t, l) for _, t, l in _seq2seq_continuations(_seq2seq_tiny_model(ns, seed), seed)]
+        print(f"seed {seed}: " + "; ".join(f"same {a}, margin {b:.1e}, new {c}, distinct {d}, no PAD {e}" for a, b, c, d, e in res))
+        if all(a and b >= 1e-3 and c >= 8 and d >= 4 and e for a, b, c, d, e in res) and _seq2seq_both_stops([r[2] for r in res]):
+            return seed
+    raise SystemExit("no seed met the conditions")
+
+
+def gen_seq2seq():
+    """(a) one training step of the notebook's model (cell 14's loop body, Adam of cell 13) on a ragged [3, .] batch; (b) the token
+    lists of the predict() loop for three sources of different lengths with the float64 restatement's logits of every step."""
+    seed_layers(117)
+    ns = _seq2seq_namespace()
+    c = SEQ2SEQ_TINY_CFG
+    model = _seq2seq_tiny_model(ns, SEQ2SEQ_TINY_SEED)
+    # a checkpoint written BY THE REFERENCE (neunet.save = pickle of state_dict()): data only, under the reference's key names
+    neunet.save(model.state_dict(), os.path.join(OUT, "seq2seq_tiny_state.pkl"))
+    arrs = dict(cfg=np.array([c["vocab"], c["d_model"], c["n_heads"], c["d_ff"], c["n_layers"], c["max_len"]], np.int64),
+                seed=np.int64(SEQ2SEQ_TINY_SEED), max_length=np.int64(SEQ2SEQ_MAX_LENGTH), names=np.array(list(model.state_dict())))
+    # ---- (b) first: the continuations of the UNTRAINED weights (the step below changes them)
+    new_counts = []
+    for i, (src, tokens, logits64) in enumerate(_seq2seq_continuations(model, SEQ2SEQ_TINY_SEED)):
+        new_counts.append(len([t for t in tokens[1:] if t != SEQ2SEQ_EOS]))
+        same, margin, n_new, distinct, no_pad = _seq2seq_greedy_ok(tokens, logits64)
+        # the fixture's conditions (tests/test_seq2seq.py re-asserts them on the stored arrays); no step is exempt
+        assert same, f"sentence {i}: the float64 restatement picks other tokens than the reference's float32 loop"
+        assert margin >= 1e-3, f"sentence {i}: greedy margin {margin:.2e} < 1e-3 of the step's largest |logit|"
+        assert n_new >= 8 and distinct >= 4, f"sentence {i}: {n_new} new tokens, {distinct} distinct"
+        assert no_pad, f"sentence {i}: the continuation contains PAD"
+        arrs.update({f"src{i}": np.asarray(src, np.int32), f"tokens{i}": np.asarray(tokens, np.int32), f"logits64_{i}": logits64})
+    assert _seq2seq_both_stops(new_counts), f"new tokens per sentence {new_counts}: one must stop at EOS and one at max_length"
+    # ---- (a) one training step on ragged sources and targets with PAD tails
+    rng = np.random.default_rng(28)
+    pad = lambda rows: np.array([r + [SEQ2SEQ_PAD] * (max(map(len, rows)) - len(r)) for r in rows], dtype=np.int64)  # noqa: E731
+    mk = lambda n: [SEQ2SEQ_SOS] + rng.integers(3, c["vocab"], n - 2).tolist() + [SEQ2SEQ_EOS]  # noqa: E731
+    src, tgt = pad([mk(7), mk(10), mk(4)]), pad([mk(9), mk(6), mk(8)])
+    model.train()
+    params = model.parameters()
+    assert len(params) == len(model.state_dict())
+    p0 = [p.data.copy() for p in params]
+    opt = Adam(params, lr=3e-4, betas=(0.9, 0.98), eps=1e-9)
+    output, attn = model.forward(src, tgt[:, :-1])
+    logits = output.data.copy()
+    output = output.reshape(output.shape[0] * output.shape[1], output.shape[2])
+    loss = nn.CrossEntropyLoss(ignore_index=SEQ2SEQ_PAD)(output, neunet.tensor(tgt[:, 1:].flatten(), dtype=neunet.int32))
+    loss.backward()
+    grads = [p.grad.copy() for p in params]
+    opt.step()
+    arrs.update(batch_src=src, batch_tgt=tgt, logits=logits, loss=np.float64(loss.data), attn=attn.data.copy(),
+                n_params=np.int64(len(params)))
+    save("seq2seq_tiny", **arrs)
+    big = {}
+    for i, (a, g, p) in enumerate(zip(p0, grads, params)):
+        big[f"p{i}"], big[f"g{i}"], big[f"p_after{i}"] = a, g.reshape(a.shape), p.data.copy()
+    save_parts("seq2seq_tiny_step", big)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
-              gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm]
+              gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq]
 
 
 def generate_all(out_dir=None, quiet=False):
@@ -853,7 +1018,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="write the fixtures here instead of tests/golden")
     ap.add_argument("--search-gpt2-seed", action="store_true", help="print the first seed that meets gen_gpt2's conditions and stop")
+    ap.add_argument("--search-seq2seq-seed", action="store_true", help="print the first seed that meets gen_seq2seq's conditions and stop")
     a = ap.parse_args()
+    if a.search_seq2seq_seed:
+        print("SEQ2SEQ_TINY_SEED =", search_seq2seq_seed())
+        sys.exit(0)
     if a.search_gpt2_seed:
         print("GPT2_TINY_SEED =", search_gpt2_seed())
         sys.exit(0)
