@@ -614,6 +614,42 @@ int nnhipMSELossForwardBackward(const float* pred, const float* target, float* l
 int nnhipMSELossSigmoidForwardBackward(const float* pred, const float* target, float* loss, float* dz_out, int64_t n,
                                        nnhipStream_t stream);
 
+/* ---- the MLP generative examples (examples/gan.ipynb, examples/vae.ipynb).  ABI 218 ---------------------------------------
+ * BatchNorm1d (neunet/nn/layers/batchnorm1d.py:46-99 forward, 15-41 backward), X [N,F] row-major (csrc/batchnorm1d.hip).
+ * training != 0: batch mean and BIASED variance over axis 0, two passes (np.var); running = momentum*running + (1-momentum)*stat
+ * (the reference's convention, :76-81; running_* may both be NULL); else mean / variance are the running statistics.  save_mean /
+ * save_inv [F] are written in BOTH modes: the backward is the reference's one formula whatever the mode (in eval it reads
+ * X - running_mean and treats that mean and 1/std as batch statistics).  weight / bias [F] may both be NULL (affine = False), and
+ * so may dW / db.  One launch per call; no workspace, no atomics, no host synchronisation (legal inside a stream capture); sums
+ * in a fixed order (reruns are bit-identical).  Features run along the lanes and a block owns a strip of features: a column is
+ * NEVER split across blocks, so a very tall, narrow input (N >> 10^4 with a few features) is a few blocks walking long columns --
+ * slow by construction.  1 <= N < 2^31, 1 <= F < 2^31, else NNHIP_EINVAL.  N = 1 in training: var = 0, Y = bias, dX = 0. */
+int nnhipBatchNorm1dForward(const float* X, const float* weight, const float* bias, float* Y, float* save_mean,
+                            float* save_inv, float* running_mean, float* running_var, int64_t N, int64_t F, float eps,
+                            float momentum, int training, nnhipStream_t stream);
+int nnhipBatchNorm1dBackward(const float* dY, const float* X, const float* weight, const float* save_mean,
+                             const float* save_inv, float* dX, float* dW, float* db, int64_t N, int64_t F,
+                             nnhipStream_t stream);
+/* Tanh (neunet/nn/activations.py:107-126): out = tanh(in) ; dIn = dOut * (1 - out^2), `out` = forward output. */
+int nnhipTanhForward(float* out, const float* in, int64_t size, nnhipStream_t stream);
+int nnhipTanhBackward(float* dIn, const float* dOut, const float* out, int64_t size, nnhipStream_t stream);
+/* BCELoss (neunet/nn/losses.py:36-53): term = -(y log p + (1-y) log(1-p)) * w, the reference's expression literally (no clamp:
+ * p = 0 or 1 gives inf / NaN as np.log does).  w = weight[i] (an array of n) or, weight == NULL, weight_scalar.  reduction 'm':
+ * loss[0] = sum / n, 's': loss[0] = sum, 'n': loss[0..n) = the terms.  dpred (may be NULL) = d(loss)/dpred, scale = 1/n for 'm',
+ * else 1: -(y/p - (1-y)/(1-p)) w scale; sigmoid_fold != 0: pred is a Sigmoid's output and dpred receives the gradient of the
+ * Sigmoid's INPUT, (p - y) w scale (losses.py composed with activations.py:12-13) -- finite at a saturated p. */
+int nnhipBCELossForwardBackward(const float* pred, const float* target, const float* weight, float weight_scalar, float* loss,
+                                float* dpred, int64_t n, char reduction, int sigmoid_fold, nnhipStream_t stream);
+/* The VAE's latent expressions (examples/vae.ipynb: VAE.reparameterize, VAE.loss_function).
+ * Reparameterisation: std_out = exp(logvar / 2), z = mu + eps * std_out ; backward dmu = dz, dlogvar = dz * eps * 0.5 * std.
+ * KL term: loss[0] = -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) ; dmu = mu, dlogvar = 0.5 (exp(logvar) - 1) (both may be NULL). */
+int nnhipGaussianReparamForward(const float* mu, const float* logvar, const float* eps, float* z, float* std_out, int64_t n,
+                                nnhipStream_t stream);
+int nnhipGaussianReparamBackward(const float* dz, const float* eps, const float* std_saved, float* dmu, float* dlogvar, int64_t n,
+                                 nnhipStream_t stream);
+int nnhipGaussianKLDForwardBackward(const float* mu, const float* logvar, float* loss, float* dmu, float* dlogvar, int64_t n,
+                                    nnhipStream_t stream);
+
 /* ---- gradient-bucket helpers for data-parallel training (net-new) ---------------- */
 /* x[i] *= alpha */
 int nnhipScale(float* x, float alpha, int64_t n, nnhipStream_t stream);

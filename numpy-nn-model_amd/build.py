@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "sample.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "sample.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
@@ -47,7 +47,10 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             # would put either in scratch (every instantiation, the unaligned one included)
             "linear_gemv.hip": (r"linear_gemv_kernel",),
             # the stride-phase ConvTranspose2d forward: conv_tap_kernel's pipeline (64 accumulator registers + two tiles in flight)
-            "conv_transpose.hip": (r"conv_phase_kernel",)}
+            "conv_transpose.hip": (r"conv_phase_kernel",),
+            # BatchNorm1d: the register tier keeps a strip's column segment (16 values per lane, 32 in the backward) in registers between
+            # its passes, and the looped tier is nothing but streaming loads: a spill would put either in scratch
+            "batchnorm1d.hip": (r"bn1_",)}
 # The 2-wave-block attention kernels (head dim 64) sit exactly at the 256-VGPR limit of 2 waves per SIMD and keep two or
 # three values in scratch (8-12 B/lane; measured 4-6 % FASTER than the 4-wave blocks all the same): tolerated up to here.
 SPILL_ALLOWANCE = ((r"attn_\w+_kernelILi64ELb0ELi2E", 16),)

@@ -141,6 +141,10 @@ struct GeluB {
         return dy * (t == 0.f ? s : fmaf(t, 2.f * kGeluK * fmaf(3.f * kGeluC, x2, 1.f), s));   // x^2 overflows for |x| > 1.8e19 (0 * inf)
     }
 };
+// f = tanh(x)                 (neunet/nn/activations.py:118-120)
+struct TanhF { __device__ float operator()(float x) const { return tanhf(x); } };
+// dIn = dOut * (1 - f^2), f the activation's OUTPUT   (neunet/nn/activations.py:107-110)
+struct TanhB { __device__ float operator()(float dy, float f) const { return dy * (1.0f - f * f); } };
 struct ScaleF {
     float alpha;
     __device__ float operator()(float x) const { return alpha * x; }
@@ -306,6 +310,18 @@ extern "C" int nnhipGELUBackward(float* dIn, const float* dOut, const float* in,
     if (size == 0) return 0;
     NNHIP_PTRS("nnhipGELUBackward", dIn, dOut, in);
     return launch_map2(dIn, dOut, in, size, GeluB{}, (hipStream_t)s, "gelu_backward");
+}
+extern "C" int nnhipTanhForward(float* out, const float* in, int64_t size, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipTanhForward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipTanhForward", out, in);
+    return launch_map1(out, in, size, TanhF{}, (hipStream_t)s, "tanh_forward");
+}
+extern "C" int nnhipTanhBackward(float* dIn, const float* dOut, const float* out, int64_t size, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipTanhBackward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipTanhBackward", dIn, dOut, out);
+    return launch_map2(dIn, dOut, out, size, TanhB{}, (hipStream_t)s, "tanh_backward");
 }
 extern "C" int nnhipFusedSwishAndMul(float* out, const float* in, float beta, int64_t hidden,
                                      int64_t size, nnhipStream_t s) {

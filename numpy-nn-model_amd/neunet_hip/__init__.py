@@ -215,6 +215,73 @@ def add_channel_bias(h: Tensor, t: Tensor) -> Tensor:
     return out
 
 
+def reparameterize(mu: Tensor, logvar: Tensor, eps: Tensor) -> Tensor:
+    """z = mu + eps * exp(logvar / 2) -- VAE.reparameterize of the reference's examples/vae.ipynb (which writes it as
+    logvar.mul(0.5).exp(), eps * std, mu + ...: three tape nodes) as ONE launch forward (nnhipGaussianReparamForward) and one backward:
+    dmu = grad, dlogvar = grad * eps * 0.5 * std.  eps is a tensor the caller draws (the notebook draws it with the host NumPy RNG);
+    it receives no gradient."""
+    import torch
+    from ._lib import call_hip_function, get_current_stream_ptr
+    if not all(isinstance(t, Tensor) for t in (mu, logvar, eps)):
+        raise TypeError("reparameterize takes Tensors")
+    if not (mu.device == logvar.device == eps.device == "cuda"):
+        raise ValueError("reparameterize needs its three tensors on the HIP device ('cuda')")
+    if not (tuple(mu.shape) == tuple(logvar.shape) == tuple(eps.shape)):
+        raise ValueError(f"reparameterize needs equal shapes (got {mu.shape}, {logvar.shape}, {eps.shape})")
+    if any(t.dtype != "float32" for t in (mu, logvar, eps)):
+        raise NotImplementedError("Only float32 is supported")
+    md, ld, ed = (t.data.contiguous() for t in (mu, logvar, eps))
+    z, std = torch.empty_like(md), torch.empty_like(md)
+    call_hip_function("nnhipGaussianReparamForward", md, ld, ed, z, std, z.numel(), get_current_stream_ptr())
+    rg = mu.requires_grad or logvar.requires_grad
+    out = Tensor(z, (mu, logvar) if rg else None, "reparameterize", requires_grad=rg, device="cuda", _nocopy=True)
+
+    def grad_fn(a, b, grad):
+        dmu, dlv = torch.empty_like(md), torch.empty_like(md)
+        call_hip_function("nnhipGaussianReparamBackward", grad.contiguous(), ed, std, dmu, dlv, dmu.numel(), get_current_stream_ptr())
+        a.apply_grad(dmu)
+        b.apply_grad(dlv)
+
+    out.grad_fn = grad_fn
+    return out
+
+
+class _KLDTensor(Tensor):
+    _implicit_seed = True      # backward() with no argument needs no ones tensor (as the fused loss tensors)
+
+
+def gaussian_kld(mu: Tensor, logvar: Tensor) -> Tensor:
+    """KLD = -0.5 * sum(1 + logvar - mu^2 - exp(logvar)), a 0-d tensor -- VAE.loss_function of examples/vae.ipynb; value and both
+    gradients (dmu = mu, dlogvar = 0.5 (exp(logvar) - 1), times the upstream gradient) from one launch (nnhipGaussianKLDForwardBackward)."""
+    import torch
+    from ._lib import call_hip_function, get_current_stream_ptr
+    from .nn.experimental.utils import times_upstream
+    if not isinstance(mu, Tensor) or not isinstance(logvar, Tensor):
+        raise TypeError("gaussian_kld takes Tensors")
+    if not (mu.device == logvar.device == "cuda"):
+        raise ValueError("gaussian_kld needs its tensors on the HIP device ('cuda')")
+    if tuple(mu.shape) != tuple(logvar.shape):
+        raise ValueError(f"gaussian_kld needs equal shapes (got {mu.shape} and {logvar.shape})")
+    if mu.dtype != "float32" or logvar.dtype != "float32":
+        raise NotImplementedError("Only float32 is supported")
+    md, ld = mu.data.contiguous(), logvar.data.contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=md.device)
+    dmu, dlv = torch.empty_like(md), torch.empty_like(md)
+    call_hip_function("nnhipGaussianKLDForwardBackward", md, ld, loss, dmu, dlv, md.numel(), get_current_stream_ptr())
+    rg = mu.requires_grad or logvar.requires_grad
+    out = _KLDTensor(loss, (mu, logvar) if rg else None, "gaussian_kld", requires_grad=rg, device="cuda", _nocopy=True)
+
+    def grad_fn(a, b, grad):
+        unit = getattr(out_ref(), "_seeded_with_ones", False)
+        a.apply_grad(dmu if unit else times_upstream(dmu, grad))
+        b.apply_grad(dlv if unit else times_upstream(dlv, grad))
+
+    import weakref
+    out_ref = weakref.ref(out)
+    out.grad_fn = grad_fn
+    return out
+
+
 def save(obj, path):
     """neunet.save = pickle (neunet/__init__.py:26-29)."""
     import pickle

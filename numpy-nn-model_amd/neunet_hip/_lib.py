@@ -189,6 +189,14 @@ _SIGNATURES = {
                                                          c_float, P, P, c_int64, P, P, P, P, c_void_p]),
     "nnhipMSELossForwardBackward": (ctypes.c_int, [P, P, P, P, c_int64, c_void_p]),
     "nnhipMSELossSigmoidForwardBackward": (ctypes.c_int, [P, P, P, P, c_int64, c_void_p]),
+    "nnhipBatchNorm1dForward": (ctypes.c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_float, c_float, ctypes.c_int, c_void_p]),
+    "nnhipBatchNorm1dBackward": (ctypes.c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_void_p]),
+    "nnhipTanhForward": (ctypes.c_int, [P, P, c_int64, c_void_p]),
+    "nnhipTanhBackward": (ctypes.c_int, [P, P, P, c_int64, c_void_p]),
+    "nnhipBCELossForwardBackward": (ctypes.c_int, [P, P, P, c_float, P, P, c_int64, c_char, ctypes.c_int, c_void_p]),
+    "nnhipGaussianReparamForward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
+    "nnhipGaussianReparamBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
+    "nnhipGaussianKLDForwardBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
     "nnhipScale": (ctypes.c_int, [P, c_float, c_int64, c_void_p]),
     "nnhipScaleRows": (ctypes.c_int, [P, P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipAdd": (ctypes.c_int, [P, P, P, c_int64, c_void_p]),

@@ -11,7 +11,8 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPLeakyReLU as LeakyReLU, HIPMaxPool2d as MaxPool2d, HIPMSELoss as MSELoss,
                            HIPSigmoid as Sigmoid, HIPLSTM as LSTM, HIPLayerNorm as LayerNorm, HIPGELU as GELU,
                            HIPCausalSelfAttention as CausalSelfAttention, KVCache, CrossAttentionMemory,
-                           HIPConvTranspose2d as ConvTranspose2d)
+                           HIPConvTranspose2d as ConvTranspose2d, HIPBatchNorm1d as BatchNorm1d, HIPTanh as Tanh,
+                           HIPBCELoss as BCELoss)
 
 
 class CrossEntropyLoss(HIPCrossEntropyLoss):

@@ -1,6 +1,6 @@
 """HIP activations: drop-ins for CUDASwish (experimental/activations/swish/swish.py:92-120),
 CUDAFusedSwishAndMul (.../fused_swish_and_mul/fused_swish_and_mul.py:154-179), CUDASoftmax
-(.../softmax/softmax.py:139-169), plus HIPReLU (CPU reference: neunet/nn/activations.py:40-59)."""
+(.../softmax/softmax.py:139-169), plus HIPReLU (CPU reference: neunet/nn/activations.py:40-59) and HIPTanh (:107-126)."""
 import weakref
 
 import numpy as np
@@ -155,6 +155,33 @@ class HIPGELU(Module):
         out = x.xp.empty_like(x.data)
         hip_gelu_forward(x.data, out)
         return _HIPGELUTensor(out, [x], "gelu", device=x.device)
+
+
+# ------------------------------------------------------------------------------------------- Tanh
+class _HIPTanhTensor(Tensor):
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+
+        def grad_fn(t: Tensor, f_x, grad):
+            grad_input = t.xp.empty_like(f_x)        # not t.data: t may be a Linear output that was never materialised
+            call_hip_function("nnhipTanhBackward", grad_input, contiguous(grad), f_x, f_x.numel(), get_current_stream_ptr())
+            t.apply_grad(grad_input)
+
+        self.grad_fn = grad_fn
+
+
+class HIPTanh(Module):
+    """neunet/nn/activations.py:107-126: f = tanh(x); the backward reads the saved output, dx = dy (1 - f^2)."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        require_device_f32(x)
+        xd = contiguous(x.data)
+        f_x = x.xp.empty_like(xd)
+        call_hip_function("nnhipTanhForward", f_x, xd, f_x.numel(), get_current_stream_ptr())
+        return _HIPTanhTensor(f_x, [x, f_x], "tanh", device=x.device)
 
 
 # -------------------------------------------------------------------------------- SwiGLU gate

@@ -12,7 +12,7 @@ path, all on the side of the CPU semantics (neunet/nn/losses.py:59-126):
 import weakref
 from ...autograd import Tensor
 from ..modules import Module
-from .utils import call_hip_function, contiguous, get_current_stream_ptr, times_upstream
+from .utils import call_hip_function, contiguous, get_current_stream_ptr, require_device_f32, times_upstream
 
 _RED = {"none": b"n", "mean": b"m", "sum": b"s"}
 
@@ -152,3 +152,94 @@ class HIPCrossEntropyLoss(Module):
 
 
 CUDACrossEntropyLoss = HIPCrossEntropyLoss
+
+
+# ------------------------------------------------------------------------------------------------- BCELoss
+class _HIPBCETensor(Tensor):
+    _implicit_seed = True      # backward() with no argument needs no ones tensor: grad_fn below handles the unit seed
+
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+        out_ref = weakref.ref(self)
+
+        def grad_fn(y_pred: Tensor, grad_pred, grad):
+            if getattr(out_ref(), "_seeded_with_ones", False):
+                y_pred.apply_grad(grad_pred)
+            else:
+                y_pred.apply_grad(times_upstream(grad_pred, grad))
+
+        self.grad_fn = grad_fn
+
+
+class HIPBCELoss(Module):
+    """neunet/nn/losses.py:25-56, same constructor: -(y log p + (1 - y) log(1 - p)) * weight, reduced by 'mean', 'sum' or not at all
+    ('none'); the reference's expression literally, NO clamp (p = 0 or 1 gives inf / NaN as np.log does).  weight: None, a scalar, or an
+    array / Tensor of the prediction's shape -- anything else raises ValueError (the reference accepts whatever broadcasts to the
+    prediction's shape, :41-44; the HIP path takes the two cases the kernel reads without a broadcast).  Loss and d(pred) come from one
+    pass (nnhipBCELossForwardBackward); the reduced loss is a 0-d tensor.
+
+    BCELoss(Sigmoid(z)): when the prediction is a Sigmoid's output (and NNHIP_VISION_FUSION is on) the kernel hands
+    dz = (p - y) * weight * scale straight to the Sigmoid's input, as HIPMSELoss does -- one launch less, and finite where a saturated
+    p would make the unfolded gradient 0 * inf.  The loss value is the literal expression on p either way."""
+
+    def __init__(self, weight=None, reduction="mean"):
+        super().__init__()
+        if reduction not in _RED:
+            raise ValueError("Reduction must be 'none', 'mean', or 'sum'")
+        self.weight = weight
+        self.reduction = reduction
+        self._weight_dev = None
+
+    def _weight_kind(self, shape):
+        """('scalar', value) or ('array', the weight as given): None, a scalar or a one-element array is a scalar; an array of the
+        prediction's shape is an array; anything else raises."""
+        import numpy as np
+        w = self.weight
+        if w is None:
+            return "scalar", 1.0
+        w = w.data if isinstance(w, Tensor) else w
+        if isinstance(w, (int, float, np.floating, np.integer)):
+            return "scalar", float(w)
+        if isinstance(w, (list, tuple)):
+            w = np.asarray(w, dtype=np.float32)
+        wshape = getattr(w, "shape", None)
+        if wshape is None:
+            raise ValueError("BCELoss weight must be None, a scalar, or an array of the prediction's shape")
+        if tuple(wshape) == tuple(shape):
+            return "array", w
+        if int(np.prod(tuple(wshape), dtype=np.int64)) == 1:
+            return "scalar", float(w.reshape(-1)[0])
+        raise ValueError("BCELoss weight must be None, a scalar, or an array of the prediction's shape")
+
+    def _weight_args(self, kind, w, like):
+        """(device array or None, scalar) for the kernel; the device copy of an array weight is made once."""
+        import numpy as np
+        import torch
+        if kind == "scalar":
+            return None, w
+        if self._weight_dev is None or self._weight_dev[0] is not self.weight:
+            dev = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float32)))
+            self._weight_dev = (self.weight, contiguous(dev.to(device=like.device, dtype=torch.float32)))
+        return self._weight_dev[1], 1.0
+
+    def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
+        import torch
+        from .vision import _FUSE, _HIPSigmoidTensor
+        if not isinstance(y_pred, Tensor) or not isinstance(y_true, Tensor):
+            raise TypeError("Input values must be tensors")
+        if y_pred.device != y_true.device:
+            raise ValueError("Tensors must be on the same device")
+        if y_pred.shape != y_true.shape:
+            raise ValueError("BCELoss on the HIP path needs equal shapes")
+        kind, w = self._weight_kind(y_pred.shape)
+        require_device_f32(y_pred, y_true)
+        p, t = contiguous(y_pred.data), contiguous(y_true.data)
+        w_arr, w_scalar = self._weight_args(kind, w, p)
+        none = self.reduction == "none"
+        loss = torch.empty(p.shape if none else (), dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p)
+        fold = isinstance(y_pred, _HIPSigmoidTensor) and _FUSE
+        call_hip_function("nnhipBCELossForwardBackward", p, t, w_arr, w_scalar, loss, dpred, p.numel(), _RED[self.reduction],
+                          int(fold), get_current_stream_ptr())
+        # fold: d(loss)/dz goes to the Sigmoid's input; the Sigmoid node drops out of this loss's backward
+        return _HIPBCETensor(loss, (y_pred.args[0] if fold else y_pred, dpred), "bce", device="cuda")

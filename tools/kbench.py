@@ -39,6 +39,22 @@ def bench(fn, iters, warmup=5):
     return float(np.median(ms)), float(ms.min())
 
 
+def bench_samples(fn, iters, warmup=5):
+    """Like bench(), but returns every timed launch (ms): for percentiles over the repeats of alternating routes."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        ts.append((a, b))
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) for a, b in ts]
+
+
 def report(name, med, mn, flops=None, nbytes=None):
     s = f"{name:34s} med {med:9.4f} ms  min {mn:9.4f} ms"
     if flops:
@@ -372,6 +388,47 @@ def main():
                 print(f"{'':34s} round medians {' '.join(f'{v:.4f}' for v in m)}  spread {(m.max() - m.min()) / np.median(m) * 100:.1f} %")
             report(f"convT dX         {tag}", *bench(lambda: call("nnhipConvTranspose2dBackward", X, W, dO, dX, None, None, ctypes.byref(d), st), args.iters), flops=fl)
             report(f"convT dW+db      {tag}", *bench(lambda: call("nnhipConvTranspose2dBackward", X, W, dO, None, dW, db, ctypes.byref(d), st), args.iters), flops=fl)
+
+    if "bn1d" in only:
+        # BatchNorm1d on [N, F]: the column-strip kernels (nnhipBatchNorm1d*, csrc/batchnorm1d.hip) against the only route the library
+        # had before, the BatchNorm2d entries at (N, F, 1, 1).  The two routes ALTERNATE in this process (`rounds` rounds each);
+        # per route and direction: the median of the round medians, and p10 - p90 of all timed launches.  GB/s on the algorithmic
+        # bytes (forward: read X, write Y; backward: read dY and X, write dX).  The notebooks' shapes, then two large ones.
+        rounds = 5
+        for (N, F) in [(100, 2), (100, 256), (100, 512), (1024, 1024), (8192, 512)]:
+            X, dY, w, b = randn(N, F) + 1.0, randn(N, F), rnd(F) + 1.5, rnd(F)
+            Y, dX, dW, db = (torch.empty(N, F, device=dev), torch.empty(N, F, device=dev), torch.empty(F, device=dev), torch.empty(F, device=dev))
+            sm, si, rm, rv = torch.empty(F, device=dev), torch.empty(F, device=dev), torch.zeros(F, device=dev), torch.ones(F, device=dev)
+            routes = {
+                "bn1d": (lambda: call("nnhipBatchNorm1dForward", X, w, b, Y, sm, si, rm, rv, N, F, 1e-5, 0.1, 1, st),
+                         lambda: call("nnhipBatchNorm1dBackward", dY, X, w, sm, si, dX, dW, db, N, F, st)),
+                "bn2d": (lambda: call("nnhipBatchNorm2dForward", X, w, b, Y, sm, si, rm, rv, N, F, 1, 1e-5, 0.1, 1, st),
+                         lambda: call("nnhipBatchNorm2dBackward", dY, X, w, sm, si, dX, dW, db, N, F, 1, st)),
+                # the read + write roof for the same bytes (tools/stream_roof.py's kernels at this footprint): one read and one
+                # write per element beside the forward, two reads and one write beside the backward
+                "stream": (lambda: call("nnhipReLUForward", Y, X, N * F, st), lambda: call("nnhipAdd", dX, dY, X, N * F, st))}
+            outs = {}
+            for name, (fwd, bwd) in list(routes.items())[:2]:
+                fwd()
+                bwd()
+                outs[name] = (Y.clone(), dX.clone())
+            print(f"bn1d {N}x{F}: |bn1d - bn2d| max: Y {float((outs['bn1d'][0] - outs['bn2d'][0]).abs().max()):.2e}, "
+                  f"dX {float((outs['bn1d'][1] - outs['bn2d'][1]).abs().max()):.2e}")
+            samples = {(name, k): [] for name in routes for k in (0, 1)}
+            meds = {key: [] for key in samples}
+            for _ in range(rounds):
+                for name, fns in routes.items():
+                    for k, fn in enumerate(fns):
+                        ms = bench_samples(fn, args.iters)
+                        samples[(name, k)].extend(ms)
+                        meds[(name, k)].append(float(np.median(ms)))
+            for k, direction in enumerate(("fwd", "bwd")):
+                nbytes = 4.0 * N * F * (2 if k == 0 else 3)
+                for name in routes:
+                    allms, m = np.array(samples[(name, k)]), np.array(meds[(name, k)])
+                    report(f"{name} {direction} {N}x{F}", float(np.median(m)), float(allms.min()), nbytes=nbytes)
+                    print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
+                          f"round medians {' '.join(f'{v:.4f}' for v in m)}")
 
     if want("conv"):
         for (B, Cin, H, Cout) in [(256, 1, 28, 8), (256, 8, 14, 16)]:
