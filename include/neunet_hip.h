@@ -650,6 +650,32 @@ int nnhipGaussianReparamBackward(const float* dz, const float* eps, const float*
 int nnhipGaussianKLDForwardBackward(const float* mu, const float* logvar, float* loss, float* dmu, float* dlogvar, int64_t n,
                                     nnhipStream_t stream);
 
+/* ---- vector quantisation (examples/vqvae.ipynb).  ABI 219 --------------------------------------------------------------------
+ * nnhipVQNearest replaces VQVAE.quantize: `similarity = matmul(z, codebook.weight.T)`, `distances = sum(z**2, axis=1, keepdims=True)
+ * + sum(codebook.weight**2, axis=1) - 2 * similarity`, `min_indices = argmin(distances, axis=1)`, `z_q = codebook(min_indices)`.
+ * z [N, D] and codebook [K, D] row-major.  idx[n] = the index of the code nearest to row n in squared Euclidean distance;
+ * zq[n, :] = a bit copy of codebook[idx[n], :] (zq may be NULL: indices only).  Ties and NaNs follow np.argmin: equal scores
+ * resolve to the lower index; a NaN score beats any number and the first NaN wins, so a NaN anywhere in row n gives idx[n] = 0 and
+ * a NaN in code k makes k the answer of every NaN-free row unless an earlier code holds one too.
+ * Two tiers, chosen from D alone.  D <= NNHIP_VQ_NARROW_MAX_D: one lane per row, the codebook through LDS, the score in the direct
+ * form sum_j (z_j - e_j)^2.  D > NNHIP_VQ_NARROW_MAX_D: exact-fp32 MFMA, the score in the expansion |e|^2 - 2 z.e (|z|^2 is constant
+ * in a row).  Neither form is the reference's float32 arithmetic; the guarantee is near-optimality in exact arithmetic,
+ * d(n, idx[n]) - min_k d(n, k) <= bound_n with bound_n = 2 g(D + 2) min_k d(n, k) / (1 - g(D + 2)) (narrow) and
+ * 2 g(D + 3) (|z_n| + max_k |e_k|)^2 (wide), g(m) = m 2^-24 / (1 - m 2^-24), plus a few float32 underflow quanta
+ * (csrc/vector_quantize.hip, tests/vq_ref.py).
+ * ONE launch; no workspace, no atomics, no N x K buffer, no host synchronisation (legal inside a stream capture); reruns are
+ * bit-identical.  4-byte alignment of every pointer is enough.  Rows are split over blocks and the codebook is NEVER split across
+ * blocks: a few rows against a huge codebook is one block walking all of it -- slow by construction.
+ * 1 <= N, D, K < 2^31 and z, codebook, idx non-NULL, else NNHIP_EINVAL. */
+#define NNHIP_VQ_NARROW_MAX_D 8      /* the last D of the narrow (one lane per row, direct form) tier */
+int nnhipVQNearest(const float* z, const float* codebook, int32_t* idx, float* zq, int64_t N, int64_t D, int64_t K,
+                   nnhipStream_t stream);
+/* VQVAE.loss_function's `vq_loss + beta * commit_loss` = `loss_fn(z_q, z_e.detach()) + beta * loss_fn(z_q.detach(), z_e)` (MSELoss,
+ * mean over the n elements): loss[0] = (1 + beta) sum (z_q - z_e)^2 / n ; dz_q = 2 (z_q - z_e) / n ; dz_e = 2 beta (z_e - z_q) / n
+ * (either may be NULL).  One launch of ONE block, a fixed-order sum: meant for latent tensors (a block walks the n elements). */
+int nnhipVQLossForwardBackward(const float* z_e, const float* z_q, float beta, float* loss, float* dz_e, float* dz_q, int64_t n,
+                               nnhipStream_t stream);
+
 /* ---- gradient-bucket helpers for data-parallel training (net-new) ---------------- */
 /* x[i] *= alpha */
 int nnhipScale(float* x, float alpha, int64_t n, nnhipStream_t stream);

@@ -5,6 +5,7 @@
 // That is reproduced exactly and deterministically here (atomicMax of positions, then one copy per
 // vocabulary row); it is the reference's behaviour, not the mathematical gradient.
 // The decoder's `emb * sqrt(d_model) + pe[:, :T]` (examples/gpt.ipynb cells 5-6) is fused into the gather.
+#include "arg_order.h"
 #include "common.h"
 
 namespace nnhip {
@@ -94,16 +95,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(float* __restrict__ 
 // ---- argmax (neunet.argmax -> int32, neunet/__init__.py:132-139 = np.argmax): index of the FIRST maximum along one axis of an
 // [outer, n, inner] view; a NaN counts as the maximum (NumPy: the first NaN wins).  Index results are bit-exact by construction:
 // a pure comparison network, (value, index) pairs ordered by (value desc, index asc).
-struct ArgBest {
-    float v;
-    int32_t i;
-};
-__device__ __forceinline__ bool arg_better(float v, int32_t i, float bv, int32_t bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;                     // a NaN beats any number
-    if (vn || v == bv) return i < bi;            // two NaNs, or a tie: the earlier index
-    return v > bv;
-}
+// ArgBest / arg_better: arg_order.h (shared with the nearest-code search of vector_quantize.hip, which uses the mirrored order).
 __device__ __forceinline__ ArgBest arg_wave_reduce(ArgBest b) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {

@@ -181,7 +181,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 218; }
+extern "C" int nnhipVersion(void) { return 219; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 

@@ -282,6 +282,103 @@ def gaussian_kld(mu: Tensor, logvar: Tensor) -> Tensor:
     return out
 
 
+VQ_NARROW_MAX_D = 8      # NNHIP_VQ_NARROW_MAX_D (include/neunet_hip.h): up to here the search runs one lane per row, beyond on MFMA
+
+
+def quantize(z: Tensor, codebook: Tensor, straight_through: bool = False):
+    """(z_q, indices): every row of z [..., D] replaced by the nearest row of codebook [K, D] in squared Euclidean distance, and the
+    int32 indices of those rows (shape z.shape[:-1], requires_grad=False) -- VQVAE.quantize of the reference's examples/vqvae.ipynb
+    (matmul, two norm sums, a broadcast add, argmin and an Embedding gather there) as ONE launch that never writes the N x K distance
+    matrix (nnhipVQNearest); ties and NaNs resolve as np.argmin does.
+    Gradients of z_q: a codebook that requires a gradient receives the reference's -- `Tensor.__getitem__`'s backward ASSIGNS, so a
+    code chosen by several rows keeps the gradient of the LAST of them (nnhipEmbeddingBackward, as nn.Embedding).  z receives the
+    upstream gradient unchanged if straight_through (the usual z + (z_q - z).detach(); off by default: the notebook has none) and
+    nothing otherwise.  With neither, z_q is off the tape (requires_grad=False): the notebook's case, whose codebook is a plain
+    tensor."""
+    import torch
+    from ._lib import call_hip_function, get_current_stream_ptr
+    if not isinstance(z, Tensor) or not isinstance(codebook, Tensor):
+        raise TypeError("quantize takes Tensors")
+    if z.dtype != "float32" or codebook.dtype != "float32":
+        raise NotImplementedError("Only float32 is supported")
+    if codebook.ndim != 2:
+        raise ValueError(f"quantize needs a 2-D codebook [K, D] (got {codebook.shape})")
+    if z.ndim < 1 or z.shape[-1] != codebook.shape[1]:
+        raise ValueError(f"quantize needs z [..., D] and codebook [K, D] with one D (got {z.shape} and {codebook.shape})")
+    K, D = codebook.shape
+    lead = tuple(z.shape[:-1])
+    N = int(np.prod(lead, dtype=np.int64))
+    if N == 0 or K == 0 or D == 0:
+        raise ValueError(f"quantize needs at least one row, one code and one component (got {z.shape} and {codebook.shape})")
+    if not (z.device == codebook.device == "cuda"):
+        raise ValueError("quantize needs its tensors on the HIP device ('cuda')")
+    zd, cd = z.data.contiguous(), codebook.data.contiguous()
+    zq = torch.empty_like(zd)
+    idx = torch.empty(lead, dtype=torch.int32, device=zd.device)
+    call_hip_function("nnhipVQNearest", zd, cd, idx, zq, N, D, K, get_current_stream_ptr())
+    indices = Tensor(idx, dtype=np.int32, requires_grad=False, device="cuda", _nocopy=True)
+    to_z, to_cb = bool(straight_through) and z.requires_grad, codebook.requires_grad
+    if not (to_z or to_cb):
+        return Tensor(zq, None, "quantize", requires_grad=False, device="cuda", _nocopy=True), indices
+    out = Tensor(zq, (z, codebook), "quantize", requires_grad=True, device="cuda", _nocopy=True)
+
+    def grad_fn(a, cb, grad):
+        from .nn.experimental.embedding import hip_embedding_backward
+        from .nn.experimental.linear import _finish_param, _grad_out
+        grad = grad if grad.is_contiguous() else grad.contiguous()
+        if to_cb:
+            grad_cb = _grad_out(cb, cb.data)
+            hip_embedding_backward(grad_cb, grad.reshape(N, D), idx.reshape(N), 1.0)
+            _finish_param(cb, grad_cb)
+        if to_z:
+            a.apply_grad(grad)
+
+    out.grad_fn = grad_fn
+    return out, indices
+
+
+class _VQLossTensor(Tensor):
+    _implicit_seed = True      # backward() with no argument needs no ones tensor (as the fused loss tensors)
+
+
+def vq_loss(z_e: Tensor, z_q: Tensor, beta: float = 0.25) -> Tensor:
+    """vq_loss + beta * commit_loss of VQVAE.loss_function (examples/vqvae.ipynb) = MSE(z_q, z_e.detach()) + beta * MSE(z_q.detach(), z_e),
+    a 0-d tensor: (1 + beta) mean((z_q - z_e)^2).  Value and both gradients from one launch (nnhipVQLossForwardBackward):
+    2 beta (z_e - z_q) / n goes to z_e, 2 (z_q - z_e) / n to z_q if it is on the tape, each times the upstream gradient."""
+    import torch
+    from ._lib import call_hip_function, get_current_stream_ptr
+    from .nn.experimental.utils import times_upstream
+    if not isinstance(z_e, Tensor) or not isinstance(z_q, Tensor):
+        raise TypeError("vq_loss takes Tensors")
+    if z_e.dtype != "float32" or z_q.dtype != "float32":
+        raise NotImplementedError("Only float32 is supported")
+    if tuple(z_e.shape) != tuple(z_q.shape):
+        raise ValueError(f"vq_loss needs equal shapes (got {z_e.shape} and {z_q.shape})")
+    if z_e.size == 0:
+        raise ValueError("vq_loss needs at least one element")
+    if not (z_e.device == z_q.device == "cuda"):
+        raise ValueError("vq_loss needs its tensors on the HIP device ('cuda')")
+    ed, qd = z_e.data.contiguous(), z_q.data.contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=ed.device)
+    dze = torch.empty_like(ed) if z_e.requires_grad else None
+    dzq = torch.empty_like(qd) if z_q.requires_grad else None
+    call_hip_function("nnhipVQLossForwardBackward", ed, qd, float(beta), loss, dze, dzq, ed.numel(), get_current_stream_ptr())
+    rg = z_e.requires_grad or z_q.requires_grad
+    out = _VQLossTensor(loss, (z_e, z_q) if rg else None, "vq_loss", requires_grad=rg, device="cuda", _nocopy=True)
+
+    def grad_fn(a, b, grad):
+        unit = getattr(out_ref(), "_seeded_with_ones", False)
+        if dze is not None:
+            a.apply_grad(dze if unit else times_upstream(dze, grad))
+        if dzq is not None:
+            b.apply_grad(dzq if unit else times_upstream(dzq, grad))
+
+    import weakref
+    out_ref = weakref.ref(out)
+    out.grad_fn = grad_fn
+    return out
+
+
 def save(obj, path):
     """neunet.save = pickle (neunet/__init__.py:26-29)."""
     import pickle

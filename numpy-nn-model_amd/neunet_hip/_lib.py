@@ -197,6 +197,8 @@ _SIGNATURES = {
     "nnhipGaussianReparamForward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
     "nnhipGaussianReparamBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
     "nnhipGaussianKLDForwardBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
+    "nnhipVQNearest": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipVQLossForwardBackward": (ctypes.c_int, [P, P, c_float, P, P, P, c_int64, c_void_p]),
     "nnhipScale": (ctypes.c_int, [P, c_float, c_int64, c_void_p]),
     "nnhipScaleRows": (ctypes.c_int, [P, P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipAdd": (ctypes.c_int, [P, P, P, c_int64, c_void_p]),

@@ -1255,9 +1255,131 @@ def gen_vae():
     save("vae_tiny", **arrs)
 
 
+VQVAE_TINY = {"input_size": 64, "hidden": (48, 32), "latent_size": 2, "num_embeddings": 10, "batch": 12}
+VQVAE_TINY_SEED = 17    # the first of 0, 1, 2, ... that meets _vqvae_tiny_step's conditions (python tools/gen_golden.py --search-vqvae-seed)
+
+
+def _vqvae_class():
+    """exec() the notebook's VQVAE class (cell 2) straight from /root/reference/examples/vqvae.ipynb with the two hidden widths replaced
+    -- nothing of the notebook is copied into this repository."""
+    import json
+    nb = json.load(open("/root/reference/examples/vqvae.ipynb"))
+    src = "".join(nb["cells"][2]["source"])
+    src = src[:src.index("\nvqvae = VQVAE(")]
+    h1, h2 = VQVAE_TINY["hidden"]
+    assert src.count("512") == 6 and src.count("256") == 6
+    src = src.replace("512", str(h1)).replace("256", str(h2))
+    ns = {"nn": nn, "nnet": neunet, "np": np}
+    exec(src, ns)
+    return ns["VQVAE"]
+
+
+def _vq_distances64(z, e):
+    z, e = np.asarray(z, np.float64), np.asarray(e, np.float64)
+    return ((z[:, None, :] - e[None, :, :]) ** 2).sum(-1)
+
+
+def _vqvae_tiny_step(seed, trained):
+    """One training step of the notebook's class; trained: codebook.weight rewrapped as a Parameter before the step (the notebook's own
+    is a plain tensor that requires no gradient).  Returns (arrays, conditions met)."""
+    from neunet.nn.parameter import Parameter
+    seed_layers(1300 + seed)
+    c = VQVAE_TINY
+    model = _vqvae_class()(c["input_size"], c["latent_size"], c["num_embeddings"])
+    rng = np.random.default_rng(35 + seed)
+    for seq in (model.encoder, model.decoder):                 # as _vae_tiny_step: initial biases in [0.2, 0.8] keep the ReLU columns alive
+        for m in seq.modules:
+            if isinstance(m, nn.Linear):
+                m.bias.data[...] = rng.uniform(0.2, 0.8, m.bias.data.shape).astype(F32)
+    # The codebook's amplitude is 1 / num_embeddings (0.1 here, 0.01 in the notebook), so the decoder's first Linear sees inputs that small
+    # and hands its BatchNorm1d columns of spread ~0.01, which no seed cures; its initial weights times num_embeddings bring them to O(1).
+    model.decoder.modules[0].weight.data[...] *= F32(c["num_embeddings"])
+    if trained:
+        model.codebook.weight = Parameter(model.codebook.weight)
+    params = model.parameters()
+    opt = Adam(params, lr=0.0005)
+    B = c["batch"]
+    x = rng.uniform(0, 1, (B, c["input_size"])).astype(F32)
+    codebook0 = model.codebook.weight.data.copy()
+    arrs = {"x": x, "n_params": np.int64(len(params)), "codebook": codebook0,
+            "cfg": np.array((c["input_size"],) + c["hidden"] + (c["latent_size"], c["num_embeddings"], B))}
+    for i, p in enumerate(params):
+        arrs[f"p{i}"] = p.data.copy()
+    model.train()
+    xt = neunet.tensor(x)
+    bn_inputs = []                                             # VQVAE.forward module by module, recording every BatchNorm1d input
+    z_e = _run_sequential(model.encoder, xt, bn_inputs, [])
+    z_q, min_indices = model.quantize(z_e)
+    x_recon = _run_sequential(model.decoder, z_q, bn_inputs, [])
+    loss = model.loss_function(neunet.tensor(x), x_recon, z_e, z_q)
+    opt.zero_grad()
+    loss.backward()
+    for i, p in enumerate(params):
+        arrs[f"g{i}"] = p.grad.copy()
+    opt.step()
+    for i, p in enumerate(params):
+        arrs[f"p_after{i}"] = p.data.copy()
+    bns = [m for seq in (model.encoder, model.decoder) for m in seq.modules if isinstance(m, nn.BatchNorm1d)]
+    idx = np.asarray(min_indices.data).astype(np.int32)
+    # (the five layers' running statistics end to end, in forward order: one array each keeps the file within vae_tiny.npz's size)
+    arrs.update(loss=np.float64(loss.data), x_recon=x_recon.data, z_e=z_e.data.copy(), z_q=z_q.data.copy(), indices=idx,
+                bn_running_mean=np.concatenate([m.running_mean.data.reshape(-1) for m in bns]),
+                bn_running_var=np.concatenate([m.running_var.data.reshape(-1) for m in bns]))
+    assert bool(z_q.requires_grad) == bool(trained)
+    if not trained:
+        assert np.array_equal(model.codebook.weight.data, codebook0) and model.codebook.weight.grad is None
+    d = _vq_distances64(z_e.data, codebook0)
+    two = np.sort(d, axis=1)[:, :2]
+    scale = (np.asarray(z_e.data, np.float64) ** 2).sum(1) + (codebook0.astype(np.float64) ** 2).sum(1).max()
+    counts = np.bincount(idx, minlength=c["num_embeddings"])
+    ok = (len(bn_inputs) == 5 and _bn1d_inputs_ok(bn_inputs) and bool(np.all(two[:, 1] - two[:, 0] >= 1e-3 * scale))
+          and np.array_equal(idx, d.argmin(1)) and int((counts > 0).sum()) >= 3 and int(counts.max()) >= 2)
+    return arrs, ok
+
+
+def search_vqvae_seed(limit=400):
+    for seed in range(limit):
+        if _vqvae_tiny_step(seed, False)[1] and _vqvae_tiny_step(seed, True)[1]:
+            return seed
+    raise RuntimeError("no seed meets the conditions")
+
+
+def gen_vq():
+    """vq_quantize.npz: the reference's own quantize expression (matmul, the two norm sums, argmin, the Embedding gather) on three small
+    (z, codebook) pairs, the third with a duplicated code that is some rows' nearest; vqvae_tiny_{frozen,trained}.npz: one whole
+    training step of the notebook's VQVAE class at shrunken widths -- initial parameters, codebook and input, z_e, the indices, z_q,
+    x_recon, the loss, every gradient, every parameter after Adam and the running statistics."""
+    seed_layers(121)
+    rng = np.random.default_rng(34)
+    arrs = {}
+    for tag, (N, D, K) in (("a", (7, 2, 5)), ("b", (9, 3, 12)), ("c", (11, 4, 8))):
+        z = rng.standard_normal((N, D)).astype(F32)
+        e = rng.uniform(-1, 1, (K, D)).astype(F32)
+        if tag == "c":
+            e[6] = e[1]                                        # a duplicated code ...
+            z[:3] = e[1] + F32(0.01) * rng.standard_normal((3, D)).astype(F32)      # ... that is the nearest of three rows: np.argmin says 1
+        emb = nn.Embedding(K, D)
+        emb.weight = neunet.tensor(e)
+        zt, w = neunet.tensor(z), emb.weight
+        similarity = neunet.matmul(zt, w.T)
+        distances = neunet.sum(zt ** 2, axis=1, keepdims=True) + neunet.sum(w ** 2, axis=1) - 2 * similarity
+        min_indices = neunet.argmin(distances, axis=1)
+        z_q = emb(min_indices)
+        idx = np.asarray(min_indices.data).astype(np.int32)
+        d = _vq_distances64(z, e)
+        assert np.array_equal(idx, d.argmin(1)), tag           # the float32 expression agrees with float64 on these pairs (ties included)
+        arrs.update({f"z_{tag}": z, f"codebook_{tag}": e, f"min_indices_{tag}": idx, f"z_q_{tag}": np.asarray(z_q.data, F32)})
+    assert np.all(arrs["min_indices_c"][:3] == 1)
+    save("vq_quantize", **arrs)
+    for tag, trained in (("frozen", False), ("trained", True)):
+        a, ok = _vqvae_tiny_step(VQVAE_TINY_SEED, trained)
+        assert ok, "the tiny VQ-VAE step misses its conditions (BatchNorm1d input spread, code gap, float32 = float64 indices, code use): --search-vqvae-seed"
+        save(f"vqvae_tiny_{tag}", **a)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
-              gen_batchnorm1d, gen_gan, gen_vae]
+              gen_batchnorm1d, gen_gan, gen_vae, gen_vq]
 
 
 def generate_all(out_dir=None, quiet=False):
@@ -1277,7 +1399,11 @@ if __name__ == "__main__":
     ap.add_argument("--search-seq2seq-seed", action="store_true", help="print the first seed that meets gen_seq2seq's conditions and stop")
     ap.add_argument("--search-gan-seed", action="store_true", help="print the first seed that meets gen_gan's conditions and stop")
     ap.add_argument("--search-vae-seed", action="store_true", help="print the first seed that meets gen_vae's conditions and stop")
+    ap.add_argument("--search-vqvae-seed", action="store_true", help="print the first seed that meets gen_vq's conditions and stop")
     a = ap.parse_args()
+    if a.search_vqvae_seed:
+        print("VQVAE_TINY_SEED =", search_vqvae_seed())
+        sys.exit(0)
     if a.search_gan_seed:
         print("GAN_TINY_SEED =", search_gan_seed())
         sys.exit(0)

@@ -430,6 +430,41 @@ def main():
                     print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
                           f"round medians {' '.join(f'{v:.4f}' for v in m)}")
 
+    if "vq" in only:
+        # The nearest-code search (nnhipVQNearest, csrc/vector_quantize.hip) against the composition a user would otherwise write on
+        # torch: z @ E.T, the two norms, argmin, index_select -- an N x K matrix written and read back.  The two routes and a read-only
+        # roof (a sum over z and one over the codebook: every operand byte once, nothing written) ALTERNATE in this process (`rounds`
+        # rounds each); per route: the median of the round medians and p10 - p90 of all timed launches.  Flops: 2 N K D against the
+        # fp32 MFMA peak.  The notebook's shape, two image-VQ-VAE shapes, and a wide / large-codebook one.
+        rounds = 5
+        for (N, D, K) in [(100, 2, 100), (8192, 64, 512), (32768, 64, 1024), (4096, 256, 8192)]:
+            z, E = randn(N, D), rnd(K, D)
+            idx, zq = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, D, device=dev)
+
+            def composed():
+                dist = (z * z).sum(1, keepdim=True) + (E * E).sum(1) - 2.0 * (z @ E.T)
+                i = torch.argmin(dist, dim=1)
+                return i, torch.index_select(E, 0, i)
+
+            routes = {"vq": lambda: call("nnhipVQNearest", z, E, idx, zq, N, D, K, st), "torch": composed,
+                      "read": lambda: (z.sum(), E.sum())}
+            routes["vq"]()
+            ti, _ = composed()
+            print(f"vq {N}x{D} K={K}: indices equal to the torch composition's on {float((ti.to(torch.int32) == idx).float().mean()) * 100:.3f} % "
+                  f"of the rows; N x K matrix {4.0 * N * K / 1e6:.2f} MB, codebook {4.0 * K * D / 1e6:.2f} MB")
+            samples, meds = {name: [] for name in routes}, {name: [] for name in routes}
+            for _ in range(rounds):
+                for name, fn in routes.items():
+                    ms = bench_samples(fn, args.iters)
+                    samples[name].extend(ms)
+                    meds[name].append(float(np.median(ms)))
+            for name in routes:
+                allms, m = np.array(samples[name]), np.array(meds[name])
+                report(f"{name} {N}x{D} K={K}", float(np.median(m)), float(allms.min()), flops=None if name == "read" else 2.0 * N * K * D,
+                       nbytes=4.0 * (N * D + K * D) if name == "read" else None)
+                print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
+                      f"round medians {' '.join(f'{v:.4f}' for v in m)}")
+
     if want("conv"):
         for (B, Cin, H, Cout) in [(256, 1, 28, 8), (256, 8, 14, 16)]:
             X = rnd(B, Cin, H, H)
