@@ -839,6 +839,74 @@ int nnhipAttentionDecodeCross(const float* Q, const float* Kmem, const float* Vm
 int nnhipKVMemoryFill(const float* K, const float* V, float* Kmem, float* Vmem, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                       int64_t ld, nnhipStream_t stream);
 
+/* ---- nn.GRU, nn.RNN, nn.Bidirectional (net-new exports, ABI 220; csrc/recurrent_gru.hip: the reference has no CUDA recurrences) -------
+ * GRU (CPU semantics neunet/nn/layers/gru.py:273-311 forward, :66-110 backward), gate order z, r, h (the reference's parameter order,
+ * gru.py:170-215), layout X W as for the LSTM:
+ *   z, r = rnl(X_t W_{z,r} + h_{t-1} W_h{z,r} + b),  c = nl(X_t W_h + (r * h_{t-1}) W_hh + b_h),  h_t = z h_{t-1} + (1 - z) c.
+ * RNN (rnn.py:151-159 forward, :46-56 backward):  h_t = nl(X_t W + h_{t-1} W_h + b).
+ * Derivatives are taken from the activated values (the reference's derivative(unactivated) restated); relu' is 0 at 0.
+ * ndir is 1 or 2 and every struct argument is an array of ndir structs.  Direction 1 consumes the input backwards: its step s reads
+ * X[:, T-1-s] and writes its output at index s -- what the reference's reverse_layer(X.flip(1)) yields (bidirectional.py:55-56; the
+ * reverse output is not flipped back).  Both directions of a call are ONE recurrence launch whatever T is; no flipped copy of X or
+ * dX is made, and dX [B, T, in] is the sum of the two directions' contributions, in input order.
+ * Every other buffer has a leading direction axis.  Hp = H rounded up to a multiple of 16.  1 <= H <= 512.
+ *   Y      [ndir, B, T, H]    h of step s at index s
+ *   gates  [ndir, B, T, 3Hp]  GRU only: activated z | r | c of the step that read X[:, t], at index t (columns >= H of a block: padding)
+ *   hprev  [ndir, B, T, H]    the h that met X[:, t], at index t
+ *   h0     [ndir, B, H] or NULL (zeros);  hT [ndir, B, H] or NULL: the last step's h; hT may alias h0 (cycled states)
+ *   dY     [ndir, B, T, H] (step index, as Y) and / or dYlast [ndir, B, H] (the last step's h alone); either may be NULL, not both
+ * The backward writes dX (NULL-able) and the parameter gradients (grads NULL-able, each member NULL-able; written, not accumulated).
+ * No gradient flows into h0.  A NULL bias is a zero bias.  Scratch (packed weights, dG, r * h_{t-1}, the RNN's pre-activations)
+ * comes from the library's grow-only workspace: once it has grown nothing allocates or synchronises, so every entry can be
+ * captured into a hipGraph.  No atomics: bit-identical from run to run.
+ * Refusals, all before anything is launched: a size < 1, hidden > 512, ndir outside {1, 2}, a nonlinearity code outside 0..2
+ * (NNHIP_LSTM_TANH / _SIGMOID / _RELU), a NULL X / weights / weight / Y / saved-state buffer, dY and dYlast both NULL: NNHIP_EINVAL;
+ * any pointer (struct members included) that is not 4-byte aligned: NNHIP_EALIGN. */
+typedef struct nnhipGRUWeights {
+    const float* wx[3];   /* weight_z, weight_r, weight_h     [in, H] */
+    const float* wh[3];   /* weight_hz, weight_hr, weight_hh  [H, H]  */
+    const float* b[3];    /* bias_z, bias_r, bias_h           [H]; NULL = zero */
+} nnhipGRUWeights;
+typedef struct nnhipGRUGrads {
+    float* dwx[3];
+    float* dwh[3];
+    float* db[3];
+} nnhipGRUGrads;
+typedef struct nnhipRNNWeights {
+    const float* wx;      /* weight    [in, H] */
+    const float* wh;      /* weight_h  [H, H]  */
+    const float* b;       /* bias      [H]; NULL = zero */
+} nnhipRNNWeights;
+typedef struct nnhipRNNGrads {
+    float* dwx;
+    float* dwh;
+    float* db;
+} nnhipRNNGrads;
+int nnhipGRUForward(const float* X, const nnhipGRUWeights* w, const float* h0, float* Y, float* gates, float* hprev, float* hT,
+                    int64_t B, int64_t T, int64_t in_features, int64_t hidden, int nonlinearity, int recurrent_nonlinearity,
+                    int ndir, nnhipStream_t stream);
+int nnhipGRUBackward(const float* X, const nnhipGRUWeights* w, const float* gates, const float* hprev, const float* dY,
+                     const float* dYlast, float* dX, const nnhipGRUGrads* grads, int64_t B, int64_t T, int64_t in_features,
+                     int64_t hidden, int nonlinearity, int recurrent_nonlinearity, int ndir, nnhipStream_t stream);
+int nnhipRNNForward(const float* X, const nnhipRNNWeights* w, const float* h0, float* Y, float* hprev, float* hT, int64_t B,
+                    int64_t T, int64_t in_features, int64_t hidden, int nonlinearity, int ndir, nnhipStream_t stream);
+/* Y: the forward's output (the activated states are the only saved values the RNN's backward needs besides hprev). */
+int nnhipRNNBackward(const float* X, const nnhipRNNWeights* w, const float* Y, const float* hprev, const float* dY,
+                     const float* dYlast, float* dX, const nnhipRNNGrads* grads, int64_t B, int64_t T, int64_t in_features,
+                     int64_t hidden, int nonlinearity, int ndir, nnhipStream_t stream);
+/* The merge of nn.Bidirectional (bidirectional.py:89-103; backward :16-23), one elementwise launch each way.  D, R [rows, H] are the
+ * two directions' outputs (rows = B*T, or B for the last state); out and grad are [rows, 2H] for CONCAT (last axis), else [rows, H].
+ * SUM: D + R, gradients (g, g).  MUL: D R, gradients (g R, g D).  AVG: (D + R) / 2, gradients (g / 2, g / 2).  D and R may be NULL
+ * in the backward unless the mode is MUL.  NNHIP_EINVAL: a size < 1, an unknown mode, a NULL buffer; NNHIP_EALIGN as above. */
+#define NNHIP_MERGE_CONCAT 0
+#define NNHIP_MERGE_SUM 1
+#define NNHIP_MERGE_MUL 2
+#define NNHIP_MERGE_AVG 3
+int nnhipBidirectionalMergeForward(const float* D, const float* R, float* out, int64_t rows, int64_t hidden, int mode,
+                                   nnhipStream_t stream);
+int nnhipBidirectionalMergeBackward(const float* grad, const float* D, const float* R, float* dD, float* dR, int64_t rows,
+                                    int64_t hidden, int mode, nnhipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

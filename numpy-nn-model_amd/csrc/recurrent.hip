@@ -15,31 +15,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "recurrent_common.h"
 
 namespace nnhip {
-int gemm_f32(const float* A, const float* B, float* C, const float* bias, float* preact, int64_t M, int64_t N, int64_t K, int64_t lda,
-             int64_t ldb, int64_t ldc, bool a_kmajor, bool b_kmajor, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int act,
-             float beta, hipStream_t st);
-int colsum(const float* X, int64_t rows, int64_t cols, int64_t ld, float* out, hipStream_t st);
-
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-
-constexpr int kLstmRows = 16;            // batch rows per workgroup: the M of one 16x16x4 MFMA
-constexpr int kLstmWaves = 8;            // 2 waves per SIMD
-constexpr int kLstmThreads = kLstmWaves * kWave;
-constexpr int kLstmMaxH = 512;           // 4 hidden tiles per wave; the backward's dG_t image is 16 x (4Hp + 4) floats of LDS
-
-__device__ __forceinline__ float lstm_act(int kind, float x) {
-    if (kind == NNHIP_LSTM_TANH) return tanhf(x);
-    if (kind == NNHIP_LSTM_SIGMOID) return 1.0f / (1.0f + expf(-x));
-    return fmaxf(x, 0.0f);
-}
-// derivative from the ACTIVATED value y = act(x): tanh 1 - y^2, sigmoid y (1 - y), relu [x > 0] == [y > 0] (lstm.py:457: 0 at x <= 0)
-__device__ __forceinline__ float lstm_dact_y(int kind, float y) {
-    if (kind == NNHIP_LSTM_TANH) return 1.0f - y * y;
-    if (kind == NNHIP_LSTM_SIGMOID) return y * (1.0f - y);
-    return y > 0.0f ? 1.0f : 0.0f;
-}
 
 struct LstmPack {
     const float* wx[4];
@@ -366,17 +344,6 @@ static bool lstm_resident_on() {
     return on != 0;
 }
 
-template <typename Args>
-static int lstm_run(void (*kern)(const Args), const Args& a, int64_t blocks, size_t lds, hipStream_t st, const char* name) {
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(lstm)");
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kLstmThreads), lds, st, a);
-    NNHIP_LAUNCH_CHECK(name);
-    return 0;
-}
-
 static int lstm_common_checks(const char* fn, const float* X, const nnhipLSTMWeights* w, int64_t B, int64_t T, int64_t in, int64_t H,
                               int nl, int rnl) {
     NNHIP_CHECK_ARG(B >= 1 && T >= 1 && in >= 1 && H >= 1, NNHIP_EINVAL, "%s: sizes must be positive (B %lld, T %lld, in %lld, H %lld)", fn,
@@ -439,12 +406,12 @@ extern "C" int nnhipLSTMForward(const float* X, const nnhipLSTMWeights* w, const
     a.gates = gates; a.whp = ws + in * G; a.h0 = h0; a.c0 = c0; a.Y = Y; a.cell = cell; a.hprev = hprev; a.hT = hT; a.cT = cT;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const int64_t blocks = ceil_div(B, kLstmRows);
+    const dim3 blocks((unsigned)ceil_div(B, kLstmRows));
     const size_t lds = (size_t)2 * kLstmRows * (Hp + 4) * sizeof(float);
-    if (Hp == 128 && lstm_resident_on()) return lstm_run(lstm_fwd_kernel<true, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
-    if (Hp <= 128) return lstm_run(lstm_fwd_kernel<false, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
-    if (Hp <= 256) return lstm_run(lstm_fwd_kernel<false, 2>, a, blocks, lds, st, "lstm_fwd_kernel");
-    return lstm_run(lstm_fwd_kernel<false, 4>, a, blocks, lds, st, "lstm_fwd_kernel");
+    if (Hp == 128 && lstm_resident_on()) return recurrence_run(lstm_fwd_kernel<true, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
+    if (Hp <= 128) return recurrence_run(lstm_fwd_kernel<false, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
+    if (Hp <= 256) return recurrence_run(lstm_fwd_kernel<false, 2>, a, blocks, lds, st, "lstm_fwd_kernel");
+    return recurrence_run(lstm_fwd_kernel<false, 4>, a, blocks, lds, st, "lstm_fwd_kernel");
 }
 
 extern "C" int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, const float* gates, const float* cell, const float* hprev,
@@ -471,12 +438,12 @@ extern "C" int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, cons
     a.gates = gates; a.cell = cell; a.whp = ws + in * G; a.dY = dY; a.dYlast = dYlast; a.dG = dG;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const int64_t blocks = ceil_div(B, kLstmRows);
+    const dim3 blocks((unsigned)ceil_div(B, kLstmRows));
     const size_t lds = (size_t)kLstmRows * (G + 4) * sizeof(float);
-    if (Hp == 128 && lstm_resident_on()) rc = lstm_run(lstm_bwd_kernel<true, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else if (Hp <= 128) rc = lstm_run(lstm_bwd_kernel<false, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else if (Hp <= 256) rc = lstm_run(lstm_bwd_kernel<false, 2>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else rc = lstm_run(lstm_bwd_kernel<false, 4>, a, blocks, lds, st, "lstm_bwd_kernel");
+    if (Hp == 128 && lstm_resident_on()) rc = recurrence_run(lstm_bwd_kernel<true, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
+    else if (Hp <= 128) rc = recurrence_run(lstm_bwd_kernel<false, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
+    else if (Hp <= 256) rc = recurrence_run(lstm_bwd_kernel<false, 2>, a, blocks, lds, st, "lstm_bwd_kernel");
+    else rc = recurrence_run(lstm_bwd_kernel<false, 4>, a, blocks, lds, st, "lstm_bwd_kernel");
     if (rc) return rc;
     // time-parallel part: whole-sequence GEMMs straight into the caller's gradient buffers
     if (dX && (rc = gemm_f32(dG, wxp, dX, nullptr, nullptr, BT, in, G, G, G, in, true, true, 1, 0, 0, 0, 0, 1.0f, st))) return rc;

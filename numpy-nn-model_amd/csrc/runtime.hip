@@ -156,6 +156,8 @@ static const char* device_error_text(unsigned code) {
         case NNHIP_DEVERR_KVCACHE_FULL:
             return "a KV-cache kernel (attention_decode.hip) met a row whose cache_len leaves no room for the tokens to append "
                    "(cache_len outside 0 .. Tmax - T); that row's cache and output were not written";
+        case NNHIP_DEVERR_RECURRENT_SHAPE:
+            return "a GRU / RNN recurrence kernel (recurrent_gru.hip) was launched with a shape its variant cannot hold; its outputs were not written";
         default: return "unknown device error code";
     }
 }
@@ -181,7 +183,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 219; }
+extern "C" int nnhipVersion(void) { return 220; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 

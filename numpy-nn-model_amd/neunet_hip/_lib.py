@@ -55,6 +55,26 @@ class LSTMGrads(ctypes.Structure):
     _fields_ = [("dwx", c_void_p * 4), ("dwh", c_void_p * 4), ("db", c_void_p * 4)]
 
 
+class GRUWeights(ctypes.Structure):
+    """struct nnhipGRUWeights (include/neunet_hip.h): gate order z, r, h.  The entries take an array of ndir of them."""
+    _fields_ = [("wx", c_void_p * 3), ("wh", c_void_p * 3), ("b", c_void_p * 3)]
+
+
+class GRUGrads(ctypes.Structure):
+    """struct nnhipGRUGrads (include/neunet_hip.h)."""
+    _fields_ = [("dwx", c_void_p * 3), ("dwh", c_void_p * 3), ("db", c_void_p * 3)]
+
+
+class RNNWeights(ctypes.Structure):
+    """struct nnhipRNNWeights (include/neunet_hip.h)."""
+    _fields_ = [("wx", c_void_p), ("wh", c_void_p), ("b", c_void_p)]
+
+
+class RNNGrads(ctypes.Structure):
+    """struct nnhipRNNGrads (include/neunet_hip.h)."""
+    _fields_ = [("dwx", c_void_p), ("dwh", c_void_p), ("db", c_void_p)]
+
+
 P = c_void_p  # device pointers travel as void*
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -168,6 +188,16 @@ _SIGNATURES = {
                                         ctypes.c_int, ctypes.c_int, c_void_p]),
     "nnhipLSTMBackward": (ctypes.c_int, [P, POINTER(LSTMWeights), P, P, P, P, P, P, POINTER(LSTMGrads), c_int64, c_int64, c_int64,
                                          c_int64, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "nnhipGRUForward": (ctypes.c_int, [P, POINTER(GRUWeights), P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, c_void_p]),
+    "nnhipGRUBackward": (ctypes.c_int, [P, POINTER(GRUWeights), P, P, P, P, P, POINTER(GRUGrads), c_int64, c_int64, c_int64, c_int64,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "nnhipRNNForward": (ctypes.c_int, [P, POINTER(RNNWeights), P, P, P, P, c_int64, c_int64, c_int64, c_int64, ctypes.c_int, ctypes.c_int,
+                                       c_void_p]),
+    "nnhipRNNBackward": (ctypes.c_int, [P, POINTER(RNNWeights), P, P, P, P, P, POINTER(RNNGrads), c_int64, c_int64, c_int64, c_int64,
+                                        ctypes.c_int, ctypes.c_int, c_void_p]),
+    "nnhipBidirectionalMergeForward": (ctypes.c_int, [P, P, P, c_int64, c_int64, ctypes.c_int, c_void_p]),
+    "nnhipBidirectionalMergeBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_int64, ctypes.c_int, c_void_p]),
     "nnhipLeakyReLUForward": (ctypes.c_int, [P, P, c_float, c_int64, c_void_p]),
     "nnhipLeakyReLUBackward": (ctypes.c_int, [P, P, P, c_float, c_int64, c_void_p]),
     "nnhipSigmoidForward": (ctypes.c_int, [P, P, c_int64, c_void_p]),

@@ -12,7 +12,7 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPSigmoid as Sigmoid, HIPLSTM as LSTM, HIPLayerNorm as LayerNorm, HIPGELU as GELU,
                            HIPCausalSelfAttention as CausalSelfAttention, KVCache, CrossAttentionMemory,
                            HIPConvTranspose2d as ConvTranspose2d, HIPBatchNorm1d as BatchNorm1d, HIPTanh as Tanh,
-                           HIPBCELoss as BCELoss)
+                           HIPBCELoss as BCELoss, HIPGRU as GRU, HIPRNN as RNN, HIPBidirectional as Bidirectional)
 
 
 class CrossEntropyLoss(HIPCrossEntropyLoss):

@@ -11,7 +11,7 @@ from .conv_transpose2d import HIPConvTranspose2d  # noqa: F401
 from .attention import CrossAttentionMemory, HIPMultiHeadAttention  # noqa: F401
 from .embedding import HIPDropout, HIPEmbedding, HIPPositionalEncoding  # noqa: F401
 from .vision import HIPBatchNorm2d, HIPLeakyReLU, HIPMaxPool2d, HIPMSELoss, HIPSigmoid  # noqa: F401
-from .recurrent import HIPLSTM  # noqa: F401
+from .recurrent import HIPLSTM, HIPGRU, HIPRNN, HIPBidirectional  # noqa: F401
 from .layernorm import HIPLayerNorm  # noqa: F401
 from .causal_attention import HIPCausalSelfAttention, KVCache  # noqa: F401
 from .batchnorm1d import HIPBatchNorm1d  # noqa: F401

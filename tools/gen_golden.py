@@ -1377,9 +1377,139 @@ def gen_vq():
         save(f"vqvae_tiny_{tag}", **a)
 
 
+# --------------------------------------------------------------------------- GRU / RNN / Bidirectional (recurrent_sequences_classifier.ipynb)
+_GRU_NAMES = ["weight_z", "weight_r", "weight_h", "weight_hz", "weight_hr", "weight_hh", "bias_z", "bias_r", "bias_h"]
+_RNN_NAMES = ["weight", "weight_h", "bias"]
+SEQCLS_DOCUMENT = ["Nice Clothes!", "Very good shop for clothes", "Amazing clothes", "Clothes are good", "Superb!", "Very bad",
+                   "Poor quality", "not good", "clothes fitting bad", "Shop not good"]
+
+
+def _rec_params(layer):
+    return [getattr(layer, n) for n in (_GRU_NAMES if layer.__class__.__name__ == "GRU" else _RNN_NAMES)]
+
+
+def _record_layer_case(name, layer, params, rng, B, Tn, n_in, H, modes, state, calls, backward=True):
+    """Inputs, outputs, dX and every parameter gradient of `calls` calls of a reference layer (a GRU, an RNN or a Bidirectional)."""
+    arrs = {f"p{i}": q.data.copy() for i, q in enumerate(params)}
+    arrs["cfg"] = np.array([-1 if B is None else B, Tn, n_in, H, calls])
+    arrs["modes"] = np.array([str(m) for m in modes])
+    Bx = 1 if B is None else B
+    if state:
+        arrs["h0"] = rng.uniform(-1, 1, (Bx, H)).astype(F32)
+    for c in range(calls):
+        X = rng.uniform(-1, 1, (Tn, n_in) if B is None else (B, Tn, n_in)).astype(F32)
+        x = T(X)
+        out = layer(x, arrs["h0"]) if state else layer(x)
+        outs = out if isinstance(out, tuple) else (out,)
+        arrs[f"X{c}"] = X
+        for k, o in enumerate(outs):
+            arrs[f"Y{c}_{k}"] = o.data.copy()
+            if backward:
+                dY = rng.uniform(-1, 1, o.data.shape).astype(F32)
+                o.backward(dY)
+                arrs[f"dY{c}_{k}"] = dY
+        if backward:
+            arrs[f"dX{c}"] = x.grad
+    if backward:
+        for i, q in enumerate(params):
+            arrs[f"g{i}"] = q.grad
+    save(name, **arrs)
+
+
+def gen_gru():
+    """Single reference GRU layers (neunet/nn/layers/gru.py), CPU: inputs, initial weights (biases randomised so they matter), outputs,
+    dX and all nine gradients."""
+    seed_layers(120)
+    rng = np.random.default_rng(31)
+    # name, B (None = 2-D input), T, in, H, nonlinearity, recurrent nonlinearity, return_sequences, initial state, cycled calls
+    cases = [("gru_h50_b17", 17, 12, 10, 50, "tanh", "sigmoid", "both", False, 1),
+             ("gru_t1_b1", 1, 1, 6, 16, "tanh", "sigmoid", "last", False, 1),
+             ("gru_2d", None, 5, 8, 16, "tanh", "sigmoid", "all", False, 1),
+             ("gru_state", 3, 4, 8, 16, "tanh", "sigmoid", False, True, 1),
+             ("gru_cycled", 2, 3, 8, 16, "tanh", "sigmoid", True, False, 2),
+             ("gru_relu", 4, 6, 5, 20, "relu", "tanh", "all", False, 1),
+             ("gru_relu_rec", 3, 5, 4, 24, "tanh", "relu", "last", False, 1)]
+    for name, B, Tn, n_in, H, nl, rnl, rs, state, calls in cases:
+        layer = nn.GRU(n_in, H, nonlinearity=nl, recurrent_nonlinearity=rnl, return_sequences=rs, cycled_states=calls > 1)
+        params = _rec_params(layer)
+        for b in params[6:]:
+            b.data[...] = rng.uniform(-0.3, 0.3, b.data.shape)
+        _record_layer_case(name, layer, params, rng, B, Tn, n_in, H, (nl, rnl, rs), state, calls)
+
+
+def gen_rnn():
+    """Single reference RNN layers (neunet/nn/layers/rnn.py), CPU."""
+    seed_layers(121)
+    rng = np.random.default_rng(32)
+    cases = [("rnn_h50_b17", 17, 12, 10, 50, "tanh", "both", 1),
+             ("rnn_t1_b1", 1, 1, 6, 16, "tanh", "last", 1),
+             ("rnn_relu", 4, 6, 5, 20, "relu", "all", 1),
+             ("rnn_cycled", 2, 3, 8, 16, "tanh", True, 2)]
+    for name, B, Tn, n_in, H, nl, rs, calls in cases:
+        layer = nn.RNN(n_in, H, nonlinearity=nl, return_sequences=rs, cycled_states=calls > 1)
+        params = _rec_params(layer)
+        params[2].data[...] = rng.uniform(-0.3, 0.3, params[2].data.shape)
+        _record_layer_case(name, layer, params, rng, B, Tn, n_in, H, (nl, nl, rs), False, calls)
+
+
+def gen_bidirectional():
+    """Reference Bidirectional layers (neunet/nn/layers/bidirectional.py) over a GRU or an RNN, B 3, T 5, in 7, H 20: the reverse layer's
+    parameters are re-drawn after construction (it starts as a copy of the direct layer), so the two directions differ.  p0.. are
+    the direct layer's parameters followed by the reverse layer's.  bi_gru_both is forward only: the reference's backward raises for
+    return_sequences="both" (bidirectional.py:62-73).  Then the whole notebook model, one Adam step on each of two sentences."""
+    seed_layers(122)
+    rng = np.random.default_rng(33)
+    cases = [("bi_gru_sum", "GRU", "sum", "all"), ("bi_gru_concat", "GRU", "concat", "all"), ("bi_gru_mul", "GRU", "mul", "all"),
+             ("bi_gru_avg", "GRU", "avg", "all"), ("bi_gru_last", "GRU", "sum", "last"), ("bi_rnn_sum", "RNN", "sum", "all"),
+             ("bi_gru_both", "GRU", "sum", "both")]
+    B, Tn, n_in, H = 3, 5, 7, 20
+    for name, kind, merge, rs in cases:
+        layer = nn.Bidirectional(getattr(nn, kind)(n_in, H, return_sequences=rs), merge_mode=merge)
+        direct, reverse = _rec_params(layer.direct_layer), _rec_params(layer.reverse_layer)
+        assert all(a is not b and np.array_equal(a.data, b.data) for a, b in zip(direct, reverse))
+        nw = len(direct) * 2 // 3
+        for q in reverse[:nw]:
+            q.data[...] = rng.uniform(-1, 1, q.data.shape) / np.sqrt(H)
+        for q in direct[nw:] + reverse[nw:]:
+            q.data[...] = rng.uniform(-0.3, 0.3, q.data.shape)
+        _record_layer_case(name, layer, direct + reverse, rng, B, Tn, n_in, H, (kind, merge, rs), False, 1, backward=rs != "both")
+
+    # the model of examples/recurrent_sequences_classifier.ipynb (cell 4); sentences 1 (five words) and 5 (two words, padded with 0)
+    seed_layers(123)
+    model = nn.Sequential(nn.Embedding(40, 10),
+                          nn.Bidirectional(nn.GRU(10, 50, return_sequences=True), merge_mode="sum"),
+                          nn.Bidirectional(nn.RNN(50, 50, return_sequences=True, bias=True)),
+                          nn.Bidirectional(nn.GRU(50, 50, return_sequences=False)),
+                          nn.Linear(50, 1), nn.Sigmoid())
+    params = model.parameters()
+    p0 = [q.data.copy() for q in params]
+    opt = Adam(params, lr=0.001)
+    mse = nn.MSELoss()
+    tokens = np.array([rng.permutation(np.arange(1, 40))[:5], [7, 23, 0, 0, 0]]).astype(np.int32)
+    labels = neunet.tensor(np.array([1, 0]).reshape(-1, 1))
+    arrs = dict(tokens=tokens, labels=np.array([1, 0]), n_params=np.int64(len(params)))
+    losses, outs = [], []
+    for st in range(2):
+        opt.zero_grad()
+        y = model.forward(neunet.tensor(tokens[st], dtype=neunet.int32))
+        loss = mse(y, labels[st])
+        loss.backward()
+        for i, q in enumerate(params):
+            arrs[f"g{st}_{i}"] = q.grad.copy()
+        opt.step()
+        for i, q in enumerate(params):
+            arrs[f"pf{st}_{i}"] = q.data.copy()
+        losses.append(float(loss.data))
+        outs.append(y.data.copy())
+    arrs["losses"], arrs["outs"] = np.array(losses), np.stack(outs)
+    for i, a in enumerate(p0):
+        arrs[f"p{i}"] = a
+    save_parts("seqcls_step", arrs, limit=600 * 1024)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
-              gen_batchnorm1d, gen_gan, gen_vae, gen_vq]
+              gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional]
 
 
 def generate_all(out_dir=None, quiet=False):
