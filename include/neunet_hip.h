@@ -448,6 +448,41 @@ int nnhipFusedOptimizerSetHyper(void* opt, double lr, double weight_decay, float
  * of non-ignored targets (one extra float in the gradient bucket) is the divisor -- no host read, no scale pass. */
 int nnhipFusedOptimizerSetGradDivisor(void* opt, const float* divisor_dev_or_null);
 
+/* ---- SGD, Momentum, RMSprop, Adagrad, Adadelta, Adamax, NAdam (net-new exports, ABI 221; csrc/optim_rules.hip: the reference has
+ *      no CUDA kernels for them).  CPU semantics: neunet/optim.py:76-244.  A rule moves only the streams it has:
+ *        rule      state streams            coef1     coef2   bytes / element
+ *        SGD       -                        -         -       12
+ *        MOMENTUM  s1 = m                   momentum  -       20
+ *        RMSPROP   s1 = m                   alpha     -       20
+ *        ADAGRAD   s1 = m                   -         -       20
+ *        ADADELTA  s1 = m, s2 = v           rho       -       28   (lr is not part of the reference's rule: ignored)
+ *        ADAMAX    s1 = m, s2 = v           beta1     beta2   28
+ *        NADAM     s1 = m, s2 = v           beta1     beta2   28
+ *   State pointers / tables a rule does not have may be NULL; coefficients it does not have are ignored.  Hyper-parameters are
+ *   DOUBLE and rounded to fp32 where NumPy rounds them, (1 - coef) and 1 - beta^step formed in double first, as for
+ *   nnhipFusedAdamWStep.  grad_scale multiplies g on load.  Status codes, never an exit: NNHIP_EINVAL for an unknown rule, a NULL
+ *   state pointer the rule needs, a negative size, step < 1 (per-tensor entry) or step == 0 without nnhipFusedOptimizerSetStep and
+ *   SetHyper (multi-tensor entry); n == 0 / n_tensors == 0 return 0 without a launch. */
+enum {
+    NNHIP_OPT_SGD = 0,
+    NNHIP_OPT_MOMENTUM = 1,
+    NNHIP_OPT_RMSPROP = 2,
+    NNHIP_OPT_ADAGRAD = 3,
+    NNHIP_OPT_ADADELTA = 4,
+    NNHIP_OPT_ADAMAX = 5,
+    NNHIP_OPT_NADAM = 6
+};
+/* One tensor, one launch. */
+int nnhipOptimizerRuleStep(int32_t rule, float* p, const float* g, float* s1, float* s2, int64_t n, double lr, double coef1,
+                           double coef2, double eps, int32_t step, float grad_scale, nnhipStream_t stream);
+/* All tensors in one launch, on a handle of nnhipCreateFusedOptimizer: tables and sizes as nnhipFusedAdamWMultiTensorStep, the
+ * plan re-uploaded only when it changed.  step == 0: device-driven stepping (hipGraph replay) -- the step count, lr and grad_scale
+ * come from the handle's device state (nnhipFusedOptimizerSetStep / SetHyper; the weight_decay written there is unused), and the
+ * kernel advances the step itself.  nnhipFusedOptimizerSetGradDivisor is honoured as by the Adam entry. */
+int nnhipOptimizerRuleMultiTensorStep(void* opt, int32_t rule, int32_t n_tensors, float* const* p, const float* const* g,
+                                      float* const* s1, float* const* s2, const int64_t* sizes, double lr, double coef1,
+                                      double coef2, double eps, int32_t step, float grad_scale, nnhipStream_t stream);
+
 /* ---- a3/a4 Conv2d  (net-new exports; reference CPU: neunet/nn/layers/conv2d.py:297-355, 16-115)
  *   X [B,Cin,H,W], W [Cout,Cin,kh,kw], bias [Cout] or NULL, O [B,Cout,Ho,Wo]; NCHW fp32.
  *   pad = (up, down, left, right) as Conv2d.build resolves it (conv2d.py:237-243);

@@ -18,8 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"),
+SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
 
@@ -57,7 +57,10 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             "batchnorm1d.hip": (r"bn1_",),
             # the nearest-code search keeps a row tile's operand (up to 64 registers per lane) and its running (score, index) pairs in
             # registers while the whole codebook streams past: a spill would put either in scratch
-            "vector_quantize.hip": (r"vq_",)}
+            "vector_quantize.hip": (r"vq_",),
+            # the optimizer rules are nothing but streaming loads and stores, up to four rounds of a rule's streams in flight per
+            # lane: a spill would put the loads' destinations in scratch
+            "optim_rules.hip": (r"optim_rule_",)}
 # The 2-wave-block attention kernels (head dim 64) sit exactly at the 256-VGPR limit of 2 waves per SIMD and keep two or
 # three values in scratch (8-12 B/lane; measured 4-6 % FASTER than the 4-wave blocks all the same): tolerated up to here.
 SPILL_ALLOWANCE = ((r"attn_\w+_kernelILi64ELb0ELi2E", 16),

@@ -1,4 +1,5 @@
-// optim.hip -- fused Adam / AdamW for gfx950: per-tensor launch and one-launch multi-tensor.
+// optim.hip -- fused Adam / AdamW for gfx950: per-tensor launch and one-launch multi-tensor; the optimizer handle (plan blob, device
+// state) that optim_rules.hip's seven other update rules share.
 // CPU semantics: neunet/optim.py:17-33 (Adam, L2 decay on the gradient) and :52-69 (AdamW,
 // decoupled decay).  28 B/elem of HBM traffic (read p,g,m,v; write p,m,v) -- pure bandwidth.
 #include <string.h>
@@ -7,6 +8,7 @@
 
 #include "adam_device.h"
 #include "common.h"
+#include "optim_rules_device.h"   // fused_optimizer_plan: the plan helper shared with optim_rules.hip
 
 namespace nnhip {
 
@@ -205,20 +207,14 @@ extern "C" int nnhipDestroyFusedOptimizer(void* opt) {
     return 0;
 }
 
-extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, float* const* p,
-                                              const float* const* g, float* const* m, float* const* v,
-                                              const int64_t* sizes, double lr, double beta1, double beta2,
-                                              double eps, double weight_decay, int32_t step,
-                                              int32_t decay_mode, float grad_scale, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(opt != nullptr, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: null optimizer handle");
-    if (int rc = device_error_status("nnhipFusedAdamWMultiTensorStep")) return rc;     // an earlier kernel raised the device error word
-    NNHIP_CHECK_ARG(n_tensors >= 0 && step >= 0, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: bad n_tensors/step");
-    NNHIP_CHECK_ARG(decay_mode == 0 || decay_mode == 1, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: decay_mode must be 0 or 1");
-    if (n_tensors == 0) return 0;
-    NNHIP_CHECK_ARG(p && g && m && v && sizes, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: null table");
+namespace nnhip {
+// The plan of a multi-tensor launch: [table 0][table 1]...[table n_tables-1] (n pointers each) [sizes int64 n][blk_tensor int32 nblk]
+// [blk_chunk int32 nblk], built on the host, compared bytewise with the last upload and re-sent only when something changed.
+// Adam / AdamW pass {p, g, m, v}; the rules of optim_rules.hip pass {p, g} and as many state tables as the rule has streams.
+int fused_optimizer_plan(void* opt, const char* who, int n, int n_tables, const void* const* const* tables, const int64_t* sizes,
+                         hipStream_t st, const unsigned char** dev_blob, int* nblk_out, int* chunk_out) {
     FusedOptimizer* fo = static_cast<FusedOptimizer*>(opt);
-    hipStream_t st = (hipStream_t)s;
-    const int n = n_tensors;
+    *dev_blob = nullptr; *nblk_out = 0; *chunk_out = 0;
 
     // ---- build the plan blob ------------------------------------------------------------------
     int64_t total = 0;
@@ -226,20 +222,20 @@ extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, floa
     const int64_t chunk = total >= ((int64_t)1 << 22) ? MT_CHUNK : MT_CHUNK_SMALL;
     int64_t nblk = 0;
     for (int i = 0; i < n; ++i) {
-        NNHIP_CHECK_ARG(sizes[i] >= 0, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: negative size");
-        NNHIP_CHECK_ARG(sizes[i] == 0 || (p[i] && g[i] && m[i] && v[i]), NNHIP_EINVAL,
-                        "nnhipFusedAdamWMultiTensorStep: null tensor pointer");
+        NNHIP_CHECK_ARG(sizes[i] >= 0, NNHIP_EINVAL, "%s: negative size", who);
+        bool all = true;
+        for (int t = 0; t < n_tables; ++t) all = all && tables[t][i] != nullptr;
+        NNHIP_CHECK_ARG(sizes[i] == 0 || all, NNHIP_EINVAL, "%s: null tensor pointer", who);
         nblk += ceil_div(sizes[i], chunk);
     }
     if (nblk == 0) return 0;
-    const size_t bytes = sizeof(void*) * 4 * n + sizeof(int64_t) * n + sizeof(int32_t) * 2 * (size_t)nblk;
+    NNHIP_CHECK_ARG(nblk <= 0x7fffffff, NNHIP_EINVAL, "%s: too many chunks for one launch", who);
+    const size_t ptrs = sizeof(void*) * (size_t)n_tables * n;
+    const size_t bytes = ptrs + sizeof(int64_t) * n + sizeof(int32_t) * 2 * (size_t)nblk;
     std::vector<unsigned char> blob(bytes);
-    memcpy(blob.data(), p, sizeof(void*) * n);
-    memcpy(blob.data() + sizeof(void*) * n, g, sizeof(void*) * n);
-    memcpy(blob.data() + sizeof(void*) * 2 * n, m, sizeof(void*) * n);
-    memcpy(blob.data() + sizeof(void*) * 3 * n, v, sizeof(void*) * n);
-    memcpy(blob.data() + sizeof(void*) * 4 * n, sizes, sizeof(int64_t) * n);
-    int32_t* bt = reinterpret_cast<int32_t*>(blob.data() + sizeof(void*) * 4 * n + sizeof(int64_t) * n);
+    for (int t = 0; t < n_tables; ++t) memcpy(blob.data() + sizeof(void*) * (size_t)t * n, tables[t], sizeof(void*) * n);
+    memcpy(blob.data() + ptrs, sizes, sizeof(int64_t) * n);
+    int32_t* bt = reinterpret_cast<int32_t*>(blob.data() + ptrs + sizeof(int64_t) * n);
     int32_t* bc = bt + nblk;
     int64_t b = 0;
     for (int i = 0; i < n; ++i) {
@@ -279,6 +275,32 @@ extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, floa
         fo->nblk = (int)nblk;
     }
 
+    *dev_blob = fo->dev; *nblk_out = (int)nblk; *chunk_out = (int)chunk;
+    return 0;
+}
+}  // namespace nnhip
+
+extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, float* const* p,
+                                              const float* const* g, float* const* m, float* const* v,
+                                              const int64_t* sizes, double lr, double beta1, double beta2,
+                                              double eps, double weight_decay, int32_t step,
+                                              int32_t decay_mode, float grad_scale, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(opt != nullptr, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: null optimizer handle");
+    if (int rc = device_error_status("nnhipFusedAdamWMultiTensorStep")) return rc;     // an earlier kernel raised the device error word
+    NNHIP_CHECK_ARG(n_tensors >= 0 && step >= 0, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: bad n_tensors/step");
+    NNHIP_CHECK_ARG(decay_mode == 0 || decay_mode == 1, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: decay_mode must be 0 or 1");
+    if (n_tensors == 0) return 0;
+    NNHIP_CHECK_ARG(p && g && m && v && sizes, NNHIP_EINVAL, "nnhipFusedAdamWMultiTensorStep: null table");
+    FusedOptimizer* fo = static_cast<FusedOptimizer*>(opt);
+    hipStream_t st = (hipStream_t)s;
+    const int n = n_tensors;
+    const void* const* const tables[4] = {reinterpret_cast<const void* const*>(p), reinterpret_cast<const void* const*>(g),
+                                          reinterpret_cast<const void* const*>(m), reinterpret_cast<const void* const*>(v)};
+    const unsigned char* dev_blob = nullptr;
+    int nblk = 0, chunk = 0;
+    if (int rc = fused_optimizer_plan(opt, "nnhipFusedAdamWMultiTensorStep", n, 4, tables, sizes, st, &dev_blob, &nblk, &chunk)) return rc;
+    if (nblk == 0) return 0;
+
     const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, step > 0 ? step : 1, decay_mode, grad_scale);
     float* dstate = nullptr;
     if (step == 0) {  // device-driven step counter (set with nnhipFusedOptimizerSetStep): graph-replay safe
@@ -286,8 +308,8 @@ extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, floa
                         "nnhipFusedAdamWMultiTensorStep: step == 0 needs nnhipFusedOptimizerSetStep and SetHyper first");
         dstate = fo->dev_state;
     }
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nblk), dim3(256), 0, st, fo->dev, n, (int)nblk, h, dstate, beta1,
-                       beta2, (int)chunk, fo->grad_div);
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nblk), dim3(256), 0, st, dev_blob, n, nblk, h, dstate, beta1,
+                       beta2, chunk, fo->grad_div);
     NNHIP_LAUNCH_CHECK("adamw_multi_kernel");
     return 0;
 }

@@ -177,6 +177,10 @@ _SIGNATURES = {
     "nnhipFusedOptimizerSetStep": (ctypes.c_int, [c_void_p, c_int32, c_void_p]),
     "nnhipFusedOptimizerSetHyper": (ctypes.c_int, [c_void_p, c_double, c_double, c_float, c_void_p]),
     "nnhipFusedOptimizerSetGradDivisor": (ctypes.c_int, [c_void_p, P]),
+    "nnhipOptimizerRuleStep": (ctypes.c_int, [c_int32, P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_int32, c_float, c_void_p]),
+    "nnhipOptimizerRuleMultiTensorStep": (ctypes.c_int, [c_void_p, c_int32, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                                         POINTER(c_void_p), POINTER(c_int64), c_double, c_double, c_double, c_double,
+                                                         c_int32, c_float, c_void_p]),
     "nnhipConv2dForward": (ctypes.c_int, [P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConv2dBackward": (ctypes.c_int, [P, P, P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConvTranspose2dForward": (ctypes.c_int, [P, P, P, P, POINTER(ConvTranspose2dDesc), c_void_p]),

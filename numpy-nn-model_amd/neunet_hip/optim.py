@@ -1,7 +1,8 @@
 """Fused optimizers -- drop-ins for CUDAFusedAdamW (experimental/optim/fused_adamw/fused_adamw.py:45-113)
 and CUDAFusedMultiTensorAdamW (.../fused_adamw_multitensor.py:47-148), plus `Adam` / `AdamW` names that
 select the L2-on-gradient (neunet/optim.py:17-33) or decoupled (optim.py:52-69) decay mode of the same
-fused kernel."""
+fused kernel, and the reference's seven other optimizers (optim.py:76-244: SGD, Momentum, RMSprop, Adagrad,
+Adadelta, Adamax, NAdam) on the one-launch multi-tensor kernel of csrc/optim_rules.hip."""
 import ctypes
 import weakref
 from ctypes import c_int64, c_void_p
@@ -12,13 +13,13 @@ from .autograd import bump_param_epoch
 DECOUPLED, L2_ON_GRAD = 0, 1
 
 
-def _check_params(params):
+def _check_params(params, name="Fused AdamW"):
     import torch
     for p in params:
         if p.device != "cuda":
-            raise ValueError("Fused AdamW only supports parameters on the HIP device ('cuda').")
+            raise ValueError(f"{name} only supports parameters on the HIP device ('cuda').")
         if p.data.dtype != torch.float32:
-            raise ValueError(f"Fused AdamW only supports float32 parameters, got {p.data.dtype}")
+            raise ValueError(f"{name} only supports float32 parameters, got {p.data.dtype}")
 
 
 class HIPFusedAdamW:
@@ -252,6 +253,220 @@ class Adam(HIPFusedMultiTensorAdamW):
 
     def __init__(self, params, lr: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
         super().__init__(params, lr, betas, eps, weight_decay)
+
+
+# ------------------------------------------------------------------ SGD, Momentum, RMSprop, Adagrad, Adadelta, Adamax, NAdam
+# include/neunet_hip.h: NNHIP_OPT_*
+RULE_SGD, RULE_MOMENTUM, RULE_RMSPROP, RULE_ADAGRAD, RULE_ADADELTA, RULE_ADAMAX, RULE_NADAM = range(7)
+
+
+class _RuleOptimizer:
+    """What the seven optimizers below share: one launch for all tensors (nnhipOptimizerRuleMultiTensorStep) on a handle of
+    nnhipCreateFusedOptimizer, with everything of HIPFusedMultiTensorAdamW that is not Adam's -- `grad_scale`, `grad_divisor`,
+    `use_device_step` / `sync_device_hyper` (hipGraph replay: GraphedTrainStep takes these classes as it takes Adam),
+    parameters without a gradient skipped, strided gradients copied.  A subclass names its rule, its state streams (`m`, `v`:
+    the reference's attribute names) and its two coefficients.
+
+    Never part of the optimizer-in-backward path: the README MLP's deferred backward launch applies ADAM in its epilogue, so these
+    classes do not register themselves with their parameters (`_opt_ref`), have no fuse_backward(), and answer
+    can_fuse_into_backward() False / pending_update_args() None; step() reads every gradient, which runs a still-pending
+    backward launch plain.
+
+    `t` counts step() calls in every class (the reference keeps it only where the rule has a bias correction)."""
+    rule = None
+    n_state = 0
+    _stepped_in_backward = False      # no backward kernel ever applies these rules
+
+    def _setup(self, params, lr):
+        import torch
+        self.params = list(params)
+        self.lr = lr
+        _check_params(self.params, type(self).__name__)
+        if self.n_state >= 1:
+            self.m = [torch.zeros_like(p.data) for p in self.params]
+        if self.n_state >= 2:
+            self.v = [torch.zeros_like(p.data) for p in self.params]
+        self.t = 0
+        self.grad_scale = 1.0
+        self.device_step = False      # True: step count, lr, grad_scale live on the device (hipGraph replay)
+        self._dev_hyper = None        # (lr, grad_scale) last written to the device state
+        self.grad_divisor = None      # device float tensor (1 element): gradients are divided by it inside the kernel
+        self._bound_divisor = None
+        self.opt_ptr = load_hip_function("nnhipCreateFusedOptimizer")()
+        if not self.opt_ptr:
+            raise RuntimeError("nnhipCreateFusedOptimizer failed")
+        n = len(self.params)
+        self.c_params = (c_void_p * n)()
+        self.c_grads = (c_void_p * n)()
+        self.c_state1 = (c_void_p * n)()
+        self.c_state2 = (c_void_p * n)()
+        self.c_sizes = (c_int64 * n)()
+
+    def _coefficients(self):
+        """(coef1, coef2, eps) of nnhipOptimizerRuleMultiTensorStep."""
+        return 0.0, 0.0, 0.0
+
+    def can_fuse_into_backward(self):
+        return False
+
+    def pending_update_args(self, params, step):
+        return None
+
+    def __del__(self):
+        ptr = getattr(self, "opt_ptr", None)
+        if ptr:
+            try:
+                load_hip_function("nnhipDestroyFusedOptimizer")(ptr)
+            except Exception:
+                pass
+            self.opt_ptr = None
+
+    def step(self):
+        self.t += 1
+        bump_param_epoch()        # parameters change in place: deferred Linear outputs of this step are now stale
+        idx = 0
+        keep = []        # contiguous copies of strided gradients must outlive the single launch below
+        for i, p in enumerate(self.params):
+            g = p.grad            # a backward launch still waiting for an Adam step() runs now, without an update
+            if g is None:
+                continue
+            if not g.is_contiguous():
+                g = g.contiguous()
+                keep.append(g)
+            if not p.data.is_contiguous():
+                p.data = p.data.contiguous()
+            self.c_params[idx] = p.data.data_ptr()
+            self.c_grads[idx] = g.data_ptr()
+            if self.n_state >= 1:
+                self.c_state1[idx] = self.m[i].data_ptr()
+            if self.n_state >= 2:
+                self.c_state2[idx] = self.v[i].data_ptr()
+            self.c_sizes[idx] = p.data.numel()
+            idx += 1
+        if idx == 0:
+            return
+        div = self.grad_divisor
+        if div is not self._bound_divisor:
+            call_hip_function("nnhipFusedOptimizerSetGradDivisor", self.opt_ptr, div)
+            self._bound_divisor = div
+        if self.device_step:
+            self.sync_device_hyper()
+        c1, c2, eps = self._coefficients()
+        call_hip_function("nnhipOptimizerRuleMultiTensorStep", self.opt_ptr, self.rule, idx,
+                          ctypes.cast(self.c_params, ctypes.POINTER(c_void_p)),
+                          ctypes.cast(self.c_grads, ctypes.POINTER(c_void_p)),
+                          ctypes.cast(self.c_state1, ctypes.POINTER(c_void_p)) if self.n_state >= 1 else None,
+                          ctypes.cast(self.c_state2, ctypes.POINTER(c_void_p)) if self.n_state >= 2 else None,
+                          ctypes.cast(self.c_sizes, ctypes.POINTER(c_int64)),
+                          self.lr, c1, c2, eps, 0 if self.device_step else self.t, self.grad_scale,
+                          get_current_stream_ptr())
+
+    def use_device_step(self, enable: bool = True):
+        """Move the step counter AND lr / grad_scale to device memory (needed before capturing step() into a hipGraph: host
+        values would be frozen into the captured kernel arguments).  While enabled, assign `opt.lr` and `opt.grad_scale` as
+        usual: `sync_device_hyper()` (called by step() and by GraphedTrainStep before every replay) writes changed values to the
+        device with one tiny stream-ordered launch.  The rule's coefficients and eps stay launch arguments."""
+        if enable:
+            call_hip_function("nnhipFusedOptimizerSetStep", self.opt_ptr, self.t, get_current_stream_ptr())
+            self._dev_hyper = None
+            self.device_step = True
+            self.sync_device_hyper()
+        else:
+            self.device_step = False
+
+    def sync_device_hyper(self):
+        cur = (float(self.lr), float(self.grad_scale))
+        if self.device_step and cur != self._dev_hyper:
+            call_hip_function("nnhipFusedOptimizerSetHyper", self.opt_ptr, cur[0], 0.0, cur[1], get_current_stream_ptr())
+            self._dev_hyper = cur
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+
+class SGD(_RuleOptimizer):
+    """neunet.optim.SGD (optim.py:76-90): p -= lr * g.  No state."""
+    rule, n_state = RULE_SGD, 0
+
+    def __init__(self, params, lr: float = 0.01):
+        self._setup(params, lr)
+
+
+class Momentum(_RuleOptimizer):
+    """neunet.optim.Momentum (optim.py:92-110): m = momentum * m + (1 - momentum) * g; p -= m * lr.
+    zero_grad() sets the gradients to None like every optimizer here; the reference's Momentum.zero_grad zero-fills existing
+    gradients instead (optim.py:108-110) -- the next backward pass overwrites either."""
+    rule, n_state = RULE_MOMENTUM, 1
+
+    def __init__(self, params, lr=0.01, momentum: float = 0.9):
+        self.momentum = momentum
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return self.momentum, 0.0, 0.0
+
+
+class RMSprop(_RuleOptimizer):
+    """neunet.optim.RMSprop (optim.py:113-132): m = alpha * m + (1 - alpha) * g^2; p -= lr * g / (sqrt(m) + eps)."""
+    rule, n_state = RULE_RMSPROP, 1
+
+    def __init__(self, params, lr: float = 0.01, alpha: float = 0.99, eps: float = 1e-8):
+        self.alpha, self.eps = alpha, eps
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return self.alpha, 0.0, self.eps
+
+
+class Adagrad(_RuleOptimizer):
+    """neunet.optim.Adagrad (optim.py:135-153): m += g^2; p -= lr * g / (sqrt(m) + eps)."""
+    rule, n_state = RULE_ADAGRAD, 1
+
+    def __init__(self, params, lr: float = 0.01, eps: float = 1e-8):
+        self.eps = eps
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return 0.0, 0.0, self.eps
+
+
+class Adadelta(_RuleOptimizer):
+    """neunet.optim.Adadelta (optim.py:156-181): m = rho * m + (1 - rho) * g^2; dx = -sqrt(v + eps) / sqrt(m + eps) * g;
+    v = rho * v + (1 - rho) * dx^2; p += dx.  `lr` is accepted and IGNORED: the reference stores it and never uses it."""
+    rule, n_state = RULE_ADADELTA, 2
+
+    def __init__(self, params, lr: float = 1.0, rho: float = 0.9, eps: float = 1e-6):
+        self.rho, self.eps = rho, eps
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return self.rho, 0.0, self.eps
+
+
+class Adamax(_RuleOptimizer):
+    """neunet.optim.Adamax (optim.py:184-211): m as Adam; v = max(beta2 * v, |g|); p -= lr * (m / (1 - beta1^t)) / (v + eps)."""
+    rule, n_state = RULE_ADAMAX, 2
+
+    def __init__(self, params, lr: float = 0.002, betas=(0.9, 0.999), eps: float = 1e-8):
+        self.betas, self.eps = betas, eps
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return self.betas[0], self.betas[1], self.eps
+
+
+class NAdam(_RuleOptimizer):
+    """neunet.optim.NAdam (optim.py:214-244): m, v as Adam; m_hat = m / bc1 + (1 - beta1) * g / bc1;
+    p -= lr * m_hat / (sqrt(v / bc2) + eps), bc = 1 - beta^t."""
+    rule, n_state = RULE_NADAM, 2
+
+    def __init__(self, params, lr: float = 0.002, betas=(0.9, 0.999), eps: float = 1e-8):
+        self.betas, self.eps = betas, eps
+        self._setup(params, lr)
+
+    def _coefficients(self):
+        return self.betas[0], self.betas[1], self.eps
 
 
 CUDAFusedAdamW, CUDAFusedMultiTensorAdamW = HIPFusedAdamW, HIPFusedMultiTensorAdamW

@@ -1,0 +1,179 @@
+"""CPU: the seven optimizer rules of csrc/optim_rules.hip (SGD, Momentum, RMSprop, Adagrad, Adadelta, Adamax, NAdam; ABI 221) -- the
+float32 restatement the GPU tests use (tests/optim_ref.py) against fixtures recorded from the reference (tools/gen_golden.py:
+gen_optim_rules), the new exports and their argument errors (all checked before the first device call), and the classes' signatures."""
+import ctypes
+import inspect
+
+import numpy as np
+import pytest
+
+import optim_ref
+from optim_ref import CLASS_NAMES, N_STATE, RULES
+from test_abi import lib  # noqa: F401 -- the fixture that loads (and if need be builds) the library
+
+# test_adam_golden's tolerances (tests/test_hip_parity.py): parameters, first state, second state
+RTOL, ATOL_P, ATOL_S = 1e-5, 1e-6, (1e-7, 1e-8)
+RULE_ID = {r: i for i, r in enumerate(RULES)}          # include/neunet_hip.h: NNHIP_OPT_SGD ... NNHIP_OPT_NADAM
+
+
+def check_against_fixture(g, s, params, states):
+    for i, p in enumerate(params):
+        np.testing.assert_allclose(p, g[f"p{s + 1}_{i}"], rtol=RTOL, atol=ATOL_P, err_msg=f"p step {s + 1} tensor {i}")
+        for k, name in enumerate("mv"[:len(states[i])]):
+            np.testing.assert_allclose(states[i][k], g[f"{name}{s + 1}_{i}"], rtol=RTOL, atol=ATOL_S[k], err_msg=f"{name} step {s + 1} tensor {i}")
+
+
+@pytest.mark.parametrize("rule", RULES)
+def test_restatement_reproduces_the_reference(golden, rule):
+    g = golden(f"optim_{rule}")
+    n = int(g["n_tensors"])
+    assert int(g["n_state"]) == N_STATE[rule]
+    assert float(g["lr"]) == optim_ref.DEFAULTS[rule]["lr"]
+    params = [g[f"p0_{i}"].copy() for i in range(n)]
+    states = [optim_ref.init_state(rule, p) for p in params]
+    for s in range(3):
+        for i in range(n):
+            optim_ref.step(rule, params[i], g[f"g{s}_{i}"], states[i], s + 1)
+        check_against_fixture(g, s, params, states)
+
+
+def test_mlp_fixture_layout(golden):
+    g = golden("mlp_optim_rules")
+    assert g["X"].shape == (3, 8, 20) and g["Y"].shape == (3, 8) and g["W1"].shape == (16, 20) and g["W2"].shape == (4, 16)
+    for rule in RULES:
+        assert g[f"{rule}_losses"].shape == (3,) and np.isfinite(g[f"{rule}_losses"]).all()
+        for n in ("W1", "b1", "W2", "b2"):
+            assert g[f"{rule}_{n}_final"].shape == g[n].shape and not np.array_equal(g[f"{rule}_{n}_final"], g[n])
+    # the same first batch and initial weights under every rule: the same first loss
+    assert len({float(g[f"{rule}_losses"][0]) for rule in RULES}) == 1
+
+
+def test_version_is_221(lib):
+    from neunet_hip import _lib
+    assert _lib.load_hip_function("nnhipVersion")() >= 221
+
+
+def test_new_exports_bind(lib):
+    from neunet_hip import _lib
+    for name in ("nnhipOptimizerRuleStep", "nnhipOptimizerRuleMultiTensorStep"):
+        assert hasattr(lib, name)
+        f = _lib.load_hip_function(name)
+        assert f.restype is ctypes.c_int
+    assert len(_lib._SIGNATURES["nnhipOptimizerRuleStep"][1]) == 13
+    assert len(_lib._SIGNATURES["nnhipOptimizerRuleMultiTensorStep"][1]) == 15
+
+
+def test_rule_ids_match_header():
+    import re
+    from test_abi import HEADER
+    from neunet_hip import optim
+    text = open(HEADER).read()
+    for rule in RULES:
+        value = int(re.search(r"NNHIP_OPT_%s\s*=\s*(\d+)" % rule.upper(), text).group(1))
+        assert value == RULE_ID[rule] == getattr(optim, CLASS_NAMES[rule]).rule
+        assert getattr(optim, CLASS_NAMES[rule]).n_state == N_STATE[rule]
+
+
+def test_per_tensor_argument_errors(lib):
+    """Every check precedes the first device call: the pointers here are never dereferenced."""
+    from neunet_hip._lib import NeunetHipError, call_hip_function
+    D = 0x1000                                                  # non-null, 16-byte aligned, never dereferenced
+
+    def call(rule, p=D, g=D, s1=D, s2=D, n=16, step=1):
+        return call_hip_function("nnhipOptimizerRuleStep", rule, p, g, s1, s2, n, 0.01, 0.9, 0.999, 1e-8, step, 1.0, None)
+
+    for bad in (-1, 7, 100):
+        with pytest.raises(NeunetHipError, match="unknown rule"):
+            call(bad)
+    for rule in RULES:
+        r = RULE_ID[rule]
+        with pytest.raises(NeunetHipError, match="negative size"):
+            call(r, n=-1)
+        for step in (0, -3):
+            with pytest.raises(NeunetHipError, match="step >= 1"):
+                call(r, step=step)
+        if N_STATE[rule] >= 1:
+            with pytest.raises(NeunetHipError, match="null state pointer"):
+                call(r, s1=None)
+        if N_STATE[rule] >= 2:
+            with pytest.raises(NeunetHipError, match="null state pointer"):
+                call(r, s2=None)
+        with pytest.raises(NeunetHipError, match="null pointer"):
+            call(r, p=None)
+        assert call(r, p=None, g=None, s1=None, s2=None, n=0) == 0          # nothing to do: no launch, no pointer needed
+
+
+def test_multi_tensor_argument_errors(lib):
+    from ctypes import POINTER, c_int64, c_void_p, cast
+    from neunet_hip._lib import NeunetHipError, call_hip_function, load_hip_function
+    opt = load_hip_function("nnhipCreateFusedOptimizer")()
+    assert opt
+    D = 0x1000
+    tab = cast((c_void_p * 2)(D, D), POINTER(c_void_p))
+    sizes = cast((c_int64 * 2)(16, 5), POINTER(c_int64))
+    neg = cast((c_int64 * 2)(16, -5), POINTER(c_int64))
+
+    def call(rule, handle=opt, n=2, p=tab, g=tab, s1=tab, s2=tab, sz=sizes, step=1):
+        return call_hip_function("nnhipOptimizerRuleMultiTensorStep", handle, rule, n, p, g, s1, s2, sz, 0.01, 0.9, 0.999, 1e-8, step,
+                                 1.0, None)
+
+    try:
+        with pytest.raises(NeunetHipError, match="null optimizer handle"):
+            call(0, handle=None)
+        for bad in (-1, 7):
+            with pytest.raises(NeunetHipError, match="unknown rule"):
+                call(bad)
+        for rule in RULES:
+            r = RULE_ID[rule]
+            with pytest.raises(NeunetHipError, match="negative size"):
+                call(r, sz=neg)
+            with pytest.raises(NeunetHipError, match="SetStep"):          # device-driven stepping was never set up on this handle
+                call(r, step=0)
+            with pytest.raises(NeunetHipError, match="bad n_tensors/step"):
+                call(r, step=-1)
+            with pytest.raises(NeunetHipError, match="bad n_tensors/step"):
+                call(r, n=-1)
+            if N_STATE[rule] >= 1:
+                with pytest.raises(NeunetHipError, match="null state table"):
+                    call(r, s1=None)
+            if N_STATE[rule] >= 2:
+                with pytest.raises(NeunetHipError, match="null state table"):
+                    call(r, s2=None)
+            with pytest.raises(NeunetHipError, match="null table"):
+                call(r, p=None)
+            assert call(r, n=0, p=None, g=None, s1=None, s2=None, sz=None) == 0
+    finally:
+        load_hip_function("nnhipDestroyFusedOptimizer")(opt)
+
+
+# The reference's constructors (neunet/optim.py:76-244): parameter names and defaults, in order.
+REFERENCE_SIGNATURES = {
+    "SGD": [("params", inspect.Parameter.empty), ("lr", 0.01)],
+    "Momentum": [("params", inspect.Parameter.empty), ("lr", 0.01), ("momentum", 0.9)],
+    "RMSprop": [("params", inspect.Parameter.empty), ("lr", 0.01), ("alpha", 0.99), ("eps", 1e-8)],
+    "Adagrad": [("params", inspect.Parameter.empty), ("lr", 0.01), ("eps", 1e-8)],
+    "Adadelta": [("params", inspect.Parameter.empty), ("lr", 1.0), ("rho", 0.9), ("eps", 1e-6)],
+    "Adamax": [("params", inspect.Parameter.empty), ("lr", 0.002), ("betas", (0.9, 0.999)), ("eps", 1e-8)],
+    "NAdam": [("params", inspect.Parameter.empty), ("lr", 0.002), ("betas", (0.9, 0.999)), ("eps", 1e-8)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFERENCE_SIGNATURES))
+def test_class_signatures_equal_the_reference(name):
+    from neunet_hip import optim
+    cls = getattr(optim, name)
+    sig = inspect.signature(cls)
+    assert [(p.name, p.default) for p in sig.parameters.values()] == REFERENCE_SIGNATURES[name]
+    assert all(p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for p in sig.parameters.values())
+    for method in ("step", "zero_grad", "use_device_step", "sync_device_hyper"):
+        assert callable(getattr(cls, method))
+    # never part of the optimizer-in-backward path
+    assert cls.can_fuse_into_backward(object.__new__(cls)) is False
+    assert cls.pending_update_args(object.__new__(cls), [], 1) is None
+    assert not hasattr(cls, "fuse_backward") and not hasattr(cls, "take_pending_backward")
+
+
+def test_defaults_table_matches_signatures():
+    for rule in RULES:
+        want = dict(REFERENCE_SIGNATURES[CLASS_NAMES[rule]][1:])
+        assert optim_ref.DEFAULTS[rule] == want

@@ -1507,9 +1507,82 @@ def gen_bidirectional():
     save_parts("seqcls_step", arrs, limit=600 * 1024)
 
 
+# --------------------------------------------------------------------------- SGD, Momentum, RMSprop, Adagrad, Adadelta, Adamax, NAdam
+def gen_optim_rules():
+    """optim_<rule>.npz: gen_adam's layout for the reference's seven other optimizers at their own defaults (three tensors, three
+    steps with explicit gradients, parameters and every state after every step).  mlp_optim_rules.npz: three training steps of a
+    Linear(20 -> 16) - ReLU - Linear(16 -> 4) MLP (batch 8, CrossEntropyLoss mean) from the same initial weights under each rule."""
+    import neunet.optim as ref_optim
+    seed_layers(124)
+    rng = np.random.default_rng(40)
+    shapes = [(8, 16), (1, 16), (5,)]
+    rules = [("sgd", "SGD"), ("momentum", "Momentum"), ("rmsprop", "RMSprop"), ("adagrad", "Adagrad"), ("adadelta", "Adadelta"),
+             ("adamax", "Adamax"), ("nadam", "NAdam")]
+    for tag, cname in rules:
+        params = [nn.Parameter(T(rng.standard_normal(s).astype(F32))) for s in shapes]
+        p0 = [p.data.copy() for p in params]
+        opt = getattr(ref_optim, cname)(params)
+        states = [n for n in ("m", "v") if hasattr(opt, n)]
+        arrs = {"lr": np.float64(opt.lr), "n_tensors": np.int64(len(shapes)), "n_state": np.int64(len(states))}
+        for i in range(len(shapes)):
+            arrs[f"p0_{i}"] = p0[i]
+        for s in range(3):
+            gs = [rng.standard_normal(sh).astype(F32) for sh in shapes]
+            for p, g in zip(params, gs):
+                p.grad = g
+            opt.step()
+            for i in range(len(shapes)):
+                arrs[f"g{s}_{i}"] = gs[i]
+                arrs[f"p{s + 1}_{i}"] = params[i].data.copy()
+                for n in states:
+                    arrs[f"{n}{s + 1}_{i}"] = getattr(opt, n)[i].copy()
+        assert all(a.dtype == F32 for k, a in arrs.items() if k[0] in "pgmv" and "_" in k), tag
+        save(f"optim_{tag}", **arrs)
+
+    class MLP(nn.Module):
+        def __init__(self):
+            self.l1 = nn.Linear(20, 16)
+            self.relu = nn.ReLU()
+            self.l2 = nn.Linear(16, 4)
+
+        def forward(self, x):
+            return self.l2(self.relu(self.l1(x)))
+
+    s1, s2 = 1 / np.sqrt(20), 1 / np.sqrt(16)
+    W1 = rng.uniform(-s1, s1, (16, 20)).astype(F32)
+    b1 = rng.uniform(-s1, s1, (1, 16)).astype(F32)
+    W2 = rng.uniform(-s2, s2, (4, 16)).astype(F32)
+    b2 = rng.uniform(-s2, s2, (1, 4)).astype(F32)
+    X = rng.uniform(-1, 1, (3, 8, 20)).astype(F32)
+    Y = rng.integers(0, 4, (3, 8)).astype(np.int32)
+    arrs = dict(W1=W1, b1=b1, W2=W2, b2=b2, X=X, Y=Y)
+    loss_fn = nn.CrossEntropyLoss()
+    for tag, cname in rules:
+        model = MLP()
+        set_linear(model.l1, W1, b1)
+        set_linear(model.l2, W2, b2)
+        opt = getattr(ref_optim, cname)(model.parameters())
+        losses = []
+        for s in range(3):
+            opt.zero_grad()
+            loss = loss_fn(model(T(X[s])), T(Y[s], dtype=np.int32, requires_grad=False))
+            loss.backward()
+            # RMSprop, Adagrad, Adadelta and NAdam start with steps of about lr * sign(g): a gradient that is rounding noise around
+            # zero (not an exact zero behind a dead ReLU) would make the trajectory a coin toss
+            for p in model.parameters():
+                nz = np.abs(p.grad[p.grad != 0])
+                assert nz.size == 0 or nz.min() > 1e-6, (tag, s, float(nz.min()))
+            opt.step()
+            losses.append(float(loss.data))
+        arrs[f"{tag}_losses"] = np.array(losses, dtype=np.float64)
+        for n, p in zip(("W1", "b1", "W2", "b2"), model.parameters()):
+            arrs[f"{tag}_{n}_final"] = p.data.copy()
+    save("mlp_optim_rules", **arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
-              gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional]
+              gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules]
 
 
 def generate_all(out_dir=None, quiet=False):
