@@ -184,6 +184,7 @@ int nnhipGemmF32Ex(const float* A, const float* B, float* C, const float* bias, 
                    int64_t sB2, int64_t sC2, float alpha, nnhipStream_t stream);
 
 /* ---- a12 ReLU (net-new export; reference CPU: neunet/nn/activations.py:40-59) --------------- */
+/* out = max(0, in) as np.maximum computes it: a NaN stays a NaN (it is not clamped to 0); -0.0 gives +0.0 */
 int nnhipReLUForward(float* out, const float* in, int64_t size, nnhipStream_t stream);
 /* dIn = dOut * (out > 0), `out` = forward output */
 int nnhipReLUBackward(float* dIn, const float* dOut, const float* out, int64_t size,

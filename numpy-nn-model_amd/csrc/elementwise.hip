@@ -107,7 +107,9 @@ __global__ __launch_bounds__(EW_THREADS) void map2_kernel(float* out, const floa
     }
 }
 
-struct ReluF { __device__ float operator()(float x) const { return fmaxf(x, 0.f); } };
+// f = max(0, x)               (neunet/nn/activations.py:54-56: np.maximum propagates a NaN, fmaxf(NaN, 0) would return 0 and
+// hide a diverged activation from everything downstream): one unordered compare, `not (x <= 0)` is true for x > 0 and for NaN
+struct ReluF { __device__ float operator()(float x) const { return !(x <= 0.f) ? x : 0.f; } };
 // dIn = dOut * (out > 0)      (neunet/nn/activations.py:44-45)
 struct ReluB { __device__ float operator()(float dy, float y) const { return y > 0.f ? dy : 0.f; } };
 // f = x * sigmoid(beta x)     (neunet/nn/activations.py:225-230)
