@@ -33,9 +33,10 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             # the tuned fast path: GEN = false (no dense mask / dropout); the general variants may spill a few registers
             "attention.hip": (r"attn_fwd_kernelILi\d+ELb0E", r"attn_bwd_dkdv_kernelILi\d+ELb0E", r"attn_bwd_dq_kernelILi\d+ELb0E"),
             "attention_sb.hip": (r"attn_sb_",),
-            # the LSTM recurrences up to H = 128 (the resident variants hold W_h in 128 VGPRs for the whole sequence -- a spill would put
-            # it in scratch).  The forward variants for H > 128 keep 2 / 4 hidden tiles per wave and spill today (EXPERIMENTS.md).
-            "recurrent.hip": (r"lstm_fwd_kernelILb[01]ELi1E", r"lstm_bwd_kernel"),
+            # the LSTM recurrences (the resident variants hold W_h in 128 VGPRs for the whole sequence -- a spill would put it in
+            # scratch).  The forward variants for H > 128 keep 2 / 4 hidden tiles per wave and spill today (EXPERIMENTS.md 5.9):
+            # SPILL_ALLOWANCE holds them to what they spill now
+            "recurrent.hip": (r"lstm_fwd_kernel", r"lstm_bwd_kernel"),
             # the GRU / RNN recurrences: their W_h chunks in flight, the step's saved values and the carried state are all registers -- a
             # spill would put them in scratch inside the timestep loop.  The GRU's four-tiles-per-wave instances (H > 256) sit at 256
             # VGPRs and spill today (EXPERIMENTS.md 5.19): SPILL_ALLOWANCE holds them to what they spill now
@@ -65,7 +66,9 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
 # three values in scratch (8-12 B/lane; measured 4-6 % FASTER than the 4-wave blocks all the same): tolerated up to here.
 SPILL_ALLOWANCE = ((r"attn_\w+_kernelILi64ELb0ELi2E", 16),
                    # rec_fwd_kernel<3, 4> 332 B/lane, rec_bwd_kernel<3, 4> 272 B/lane: tolerated as they stand, not beyond
-                   (r"rec_fwd_kernelILi3ELi4E", 332), (r"rec_bwd_kernelILi3ELi4E", 272))
+                   (r"rec_fwd_kernelILi3ELi4E", 332), (r"rec_bwd_kernelILi3ELi4E", 272),
+                   # lstm_fwd_kernel<false, 2> 148 B/lane, lstm_fwd_kernel<false, 4> 636 B/lane: likewise
+                   (r"lstm_fwd_kernelILb0ELi2E", 148), (r"lstm_fwd_kernelILb0ELi4E", 636))
 
 
 def check_no_spills(src, remarks):

@@ -10,44 +10,16 @@
 // The four gate weights are packed per call into [in, 4Hp] / [Hp, 4Hp] (Hp = H rounded up to 16, zero padding) in the library's
 // recurrent workspace block (arena 2): every kernel below is branch-free over the padding, and the padded columns of the saved gates
 // and of dG are finite (zero in dG), so the K = 4Hp dX GEMM is exact.
+// This file is the LSTM's step arithmetic and its two entries.  The pack, the argument checks, the tier dispatch and the backward's
+// whole-sequence GEMMs are the GRU / RNN entries' (recurrent_common.h, with ng = 4 and ndir = 1).  The non-resident MFMA loops below
+// are recurrent_gru.hip's rec_mfma_cols<4> / rec_mfma_rows written out: called as helpers they cost the two- and four-tile
+// instances 0.6-3.9 % (EXPERIMENTS.md 5.9).
 #include <stdlib.h>
-
-#include <algorithm>
 
 #include "common.h"
 #include "recurrent_common.h"
 
 namespace nnhip {
-
-struct LstmPack {
-    const float* wx[4];
-    const float* wh[4];
-    const float* b[4];
-    float* wxp;     // [in, 4Hp]   column g*Hp + j = W_x_g[:, j]
-    float* whp;     // [Hp, 4Hp]   likewise, rows >= H zero
-    float* bp;      // [4Hp]
-    int64_t in;
-    int H, Hp;
-};
-
-__global__ __launch_bounds__(256) void lstm_pack_kernel(const LstmPack p) {
-    const int64_t G = 4 * (int64_t)p.Hp;
-    const int64_t nx = p.in * G, nh = (int64_t)p.Hp * G, n = nx + nh + G;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
-        if (idx < nx) {
-            const int64_t r = idx / G;
-            const int c = (int)(idx - r * G), g = c / p.Hp, j = c - g * p.Hp;
-            p.wxp[idx] = j < p.H ? p.wx[g][r * p.H + j] : 0.0f;
-        } else if (idx < nx + nh) {
-            const int64_t e = idx - nx, r = e / G;
-            const int c = (int)(e - r * G), g = c / p.Hp, j = c - g * p.Hp;
-            p.whp[e] = (r < p.H && j < p.H) ? p.wh[g][r * p.H + j] : 0.0f;
-        } else {
-            const int c = (int)(idx - nx - nh), g = c / p.Hp, j = c - g * p.Hp;
-            p.bp[c] = (j < p.H && p.b[g]) ? p.b[g][j] : 0.0f;
-        }
-    }
-}
 
 struct LstmFwdArgs {
     float* gates;           // [B, T, 4Hp]: P (pre-activations incl. bias) on entry, activated f, i, o, g on exit
@@ -70,26 +42,19 @@ struct LstmFwdArgs {
 // RES: W_h stays in registers for the whole sequence (Hp == 128: one tile per wave, 32 k-steps x 4 gates = 128 VGPRs); otherwise
 // every step re-reads its W_h columns from L2.
 template <bool RES, int MAXT>
-__global__ __launch_bounds__(kLstmThreads, 1) void lstm_fwd_kernel(const LstmFwdArgs a) {
+__global__ __launch_bounds__(kRecThreads, 1) void lstm_fwd_kernel(const LstmFwdArgs a) {
     extern __shared__ float lds[];
     const int Hp = a.Hp, ldh = Hp + 4, G = 4 * Hp, KS = Hp / 4, ntile = Hp / 16;
-    if (Hp > MAXT * 16 * kLstmWaves || (RES && (MAXT != 1 || Hp != 128)) || blockDim.x != kLstmThreads) {
-        // impossible by the host's dispatch: leave the outputs alone and raise the library's device error word
-        if (threadIdx.x == 0 && a.err) __hip_atomic_store(a.err, (unsigned)NNHIP_DEVERR_LSTM_SHAPE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
+    if (rec_bad_shape<MAXT>(Hp, a.err, NNHIP_DEVERR_LSTM_SHAPE, RES && (MAXT != 1 || Hp != 128))) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, col = lane & 15;
-    const int b0 = blockIdx.x * kLstmRows;
-    float* hbuf[2] = {lds, lds + kLstmRows * ldh};
+    const int b0 = blockIdx.x * kRecRows;
+    float* hbuf[2] = {lds, lds + kRecRows * ldh};
 
-    for (int idx = threadIdx.x; idx < kLstmRows * Hp; idx += kLstmThreads) {
-        const int r = idx / Hp, j = idx - r * Hp, b = b0 + r;
-        hbuf[0][r * ldh + j] = (a.h0 && b < a.B && j < a.H) ? a.h0[(int64_t)b * a.H + j] : 0.0f;
-    }
+    rec_stage_state(a.h0, a.B, a.H, Hp, ldh, b0, hbuf[0]);
     float creg[MAXT][4], hreg[MAXT][4];
 #pragma unroll
     for (int tt = 0; tt < MAXT; ++tt) {
-        const int j = (wave + tt * kLstmWaves) * 16 + col;
+        const int j = (wave + tt * kRecWaves) * 16 + col;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int b = b0 + q * 4 + r;
@@ -115,7 +80,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_fwd_kernel(const LstmFwd
         float* hnext = hbuf[(t & 1) ^ 1];
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile) {                                         // wave-uniform
                 const int j = jt * 16 + col;
                 float pre[4][4];                                          // P_t of this tile, in flight under the MFMAs
@@ -168,12 +133,12 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_fwd_kernel(const LstmFwd
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = q * 4 + r, b = b0 + row;
-                    const float f = lstm_act(a.rnl, acc[0][r] + pre[0][r]);
-                    const float i = lstm_act(a.rnl, acc[1][r] + pre[1][r]);
-                    const float o = lstm_act(a.rnl, acc[2][r] + pre[2][r]);
-                    const float gg = lstm_act(a.nl, acc[3][r] + pre[3][r]);
+                    const float f = rec_act(a.rnl, acc[0][r] + pre[0][r]);
+                    const float i = rec_act(a.rnl, acc[1][r] + pre[1][r]);
+                    const float o = rec_act(a.rnl, acc[2][r] + pre[2][r]);
+                    const float gg = rec_act(a.nl, acc[3][r] + pre[3][r]);
                     const float c = f * creg[tt][r] + i * gg;
-                    const float h = o * lstm_act(a.nl, c);
+                    const float h = o * rec_act(a.nl, c);
                     const bool v = b < a.B && j < a.H;
                     if (b < a.B) {
                         float* gp = a.gates + ((int64_t)b * a.T + t) * G + j;
@@ -198,7 +163,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_fwd_kernel(const LstmFwd
     }
 #pragma unroll
     for (int tt = 0; tt < MAXT; ++tt) {
-        const int j = (wave + tt * kLstmWaves) * 16 + col;
+        const int j = (wave + tt * kRecWaves) * 16 + col;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int b = b0 + q * 4 + r;
@@ -245,15 +210,16 @@ __device__ __forceinline__ void lstm_bwd_load(const LstmBwdArgs& a, int t, int r
 // are those of its own accumulator elements.  Lane group q = lane >> 4 covers the reduction indices q Hp + s: gate q's columns.
 // RES: the wave's W_h^T slice in registers (Hp == 128: 128 VGPRs).
 template <bool RES, int MAXT>
-__global__ __launch_bounds__(kLstmThreads, 1) void lstm_bwd_kernel(const LstmBwdArgs a) {
+__global__ __launch_bounds__(kRecThreads, 1) void lstm_bwd_kernel(const LstmBwdArgs a) {
     extern __shared__ float lds[];
     const int Hp = a.Hp, G = 4 * Hp, ldg = G + 4, ntile = Hp / 16;
-    if (Hp > MAXT * 16 * kLstmWaves || (RES && (MAXT != 1 || Hp != 128)) || blockDim.x != kLstmThreads) {
+    // rec_bad_shape() written out: through the helper lstm_bwd_kernel<true, 1> takes 232 VGPRs instead of 230
+    if (Hp > MAXT * 16 * kRecWaves || (RES && (MAXT != 1 || Hp != 128)) || blockDim.x != kRecThreads) {
         if (threadIdx.x == 0 && a.err) __hip_atomic_store(a.err, (unsigned)NNHIP_DEVERR_LSTM_SHAPE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, col = lane & 15;
-    const int b0 = blockIdx.x * kLstmRows;
+    const int b0 = blockIdx.x * kRecRows;
     float wreg[RES ? 128 : 1];
     if constexpr (RES) {
         const int j = wave * 16 + col;
@@ -273,13 +239,13 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_bwd_kernel(const LstmBwd
         if constexpr (MAXT <= 2) {
 #pragma unroll
             for (int tt = 0; tt < MAXT; ++tt)
-                lstm_bwd_load(a, t, b0 + q * 4, (wave + tt * kLstmWaves) * 16 + col, gv[tt], cn[tt], cp[tt], dy[tt]);
+                lstm_bwd_load(a, t, b0 + q * 4, (wave + tt * kRecWaves) * 16 + col, gv[tt], cn[tt], cp[tt], dy[tt]);
         }
         f32x4_ acc[MAXT];
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
             acc[tt] = f32x4_{0.f, 0.f, 0.f, 0.f};
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile && t != a.T - 1) {                         // wave-uniform; no dG_{T} term at the last step
                 const float* arow = lds + col * ldg + q * Hp;
                 if constexpr (RES) {
@@ -300,13 +266,13 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_bwd_kernel(const LstmBwd
                         for (int u = 0; u < 16; ++u)
                             acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[s + u], wv[u >> 2][u & 3], acc[tt], 0, 0, 0);
                     }
+                }
             }
-        }
         }
         __syncthreads();                                              // every wave is done reading dG_{t+1}
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile) {
                     const int j = jt * 16 + col;
                     const int pt = MAXT <= 2 ? tt : 0;
@@ -317,13 +283,13 @@ __global__ __launch_bounds__(kLstmThreads, 1) void lstm_bwd_kernel(const LstmBwd
                         const bool v = b < a.B && j < a.H;
                         const float f = gv[pt][0][r], i = gv[pt][1][r], o = gv[pt][2][r], gg = gv[pt][3][r];
                         const float dh = dy[pt][r] + acc[tt][r];
-                        const float tc = lstm_act(a.nl, cn[pt][r]);
-                        const float dc = dh * o * lstm_dact_y(a.nl, tc) + dcreg[tt][r];
+                        const float tc = rec_act(a.nl, cn[pt][r]);
+                        const float dc = dh * o * rec_dact_y(a.nl, tc) + dcreg[tt][r];
                         float d[4];
-                        d[2] = dh * tc * lstm_dact_y(a.rnl, o);
-                        d[0] = dc * cp[pt][r] * lstm_dact_y(a.rnl, f);
-                        d[1] = dc * gg * lstm_dact_y(a.rnl, i);
-                        d[3] = dc * i * lstm_dact_y(a.nl, gg);
+                        d[2] = dh * tc * rec_dact_y(a.rnl, o);
+                        d[0] = dc * cp[pt][r] * rec_dact_y(a.rnl, f);
+                        d[1] = dc * gg * rec_dact_y(a.rnl, i);
+                        d[3] = dc * i * rec_dact_y(a.nl, gg);
                         dcreg[tt][r] = v ? dc * f : 0.0f;
                         float* out = a.dG + ((int64_t)b * a.T + t) * G + j;
 #pragma unroll
@@ -344,41 +310,10 @@ static bool lstm_resident_on() {
     return on != 0;
 }
 
-static int lstm_common_checks(const char* fn, const float* X, const nnhipLSTMWeights* w, int64_t B, int64_t T, int64_t in, int64_t H,
-                              int nl, int rnl) {
-    NNHIP_CHECK_ARG(B >= 1 && T >= 1 && in >= 1 && H >= 1, NNHIP_EINVAL, "%s: sizes must be positive (B %lld, T %lld, in %lld, H %lld)", fn,
-                    (long long)B, (long long)T, (long long)in, (long long)H);
-    NNHIP_CHECK_ARG(H <= kLstmMaxH, NNHIP_EINVAL, "%s: hidden_size %lld > %d is not supported", fn, (long long)H, kLstmMaxH);
-    NNHIP_CHECK_ARG(B * T < ((int64_t)1 << 31) && in < ((int64_t)1 << 31), NNHIP_EINVAL, "%s: B*T or in_features too large", fn);
-    NNHIP_CHECK_ARG(nl >= 0 && nl <= 2 && rnl >= 0 && rnl <= 2, NNHIP_EINVAL, "%s: bad nonlinearity code (%d, %d)", fn, nl, rnl);
-    NNHIP_CHECK_ARG(X && w, NNHIP_EINVAL, "%s: null X / weights", fn);
-    for (int g = 0; g < 4; ++g) {
-        NNHIP_CHECK_ARG(w->wx[g] && w->wh[g], NNHIP_EINVAL, "%s: null gate weight %d", fn, g);
-        NNHIP_CHECK_ARG(aligned4(w->wx[g]) && aligned4(w->wh[g]) && aligned4(w->b[g]), NNHIP_EALIGN, "%s: misaligned weight", fn);
-    }
-    NNHIP_CHECK_ARG(aligned4(X), NNHIP_EALIGN, "%s: misaligned X", fn);
-    return 0;
-}
-
-// packs the twelve parameters into arena 2 and returns its base: wxp [in, 4Hp] | whp [Hp, 4Hp] | bp [4Hp] | extra floats
-static float* lstm_pack(const nnhipLSTMWeights* w, int64_t in, int H, int Hp, size_t extra, hipStream_t st, int* rc) {
-    const int64_t G = 4 * (int64_t)Hp, n = (in + Hp) * G + G;
-    float* ws = static_cast<float*>(workspace_arena(2, (size_t)(n + extra) * sizeof(float)));
-    if (!ws) {
-        set_last_error("LSTM workspace allocation failed (%lld bytes)%s", (long long)((n + extra) * sizeof(float)),
-                       workspace_locked() ? " -- the workspace is locked by a captured hipGraph" : "");
-        *rc = NNHIP_ENOMEM;
-        return nullptr;
-    }
-    LstmPack p;
-    for (int g = 0; g < 4; ++g) { p.wx[g] = w->wx[g]; p.wh[g] = w->wh[g]; p.b[g] = w->b[g]; }
-    p.wxp = ws; p.whp = ws + in * G; p.bp = ws + (in + Hp) * G;
-    p.in = in; p.H = H; p.Hp = Hp;
-    const int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 1024);
-    hipLaunchKernelGGL(lstm_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-    const hipError_t e = hipGetLastError();
-    *rc = e == hipSuccess ? 0 : hip_status(e, "lstm_pack_kernel");
-    return *rc ? nullptr : ws;
+static RecWeights rec_from_lstm(const nnhipLSTMWeights* w) {
+    RecWeights out;
+    for (int g = 0; g < 4; ++g) { out.wx[g] = w->wx[g]; out.wh[g] = w->wh[g]; out.b[g] = w->b[g]; }
+    return out;
 }
 
 }  // namespace nnhip
@@ -389,16 +324,18 @@ extern "C" int nnhipLSTMForward(const float* X, const nnhipLSTMWeights* w, const
                                 float* cell, float* hprev, float* hT, float* cT, int64_t B, int64_t T, int64_t in, int64_t H, int nl,
                                 int rnl, nnhipStream_t stream) {
     const char* fn = "nnhipLSTMForward";
-    if (int rc = lstm_common_checks(fn, X, w, B, T, in, H, nl, rnl)) return rc;
+    NNHIP_CHECK_ARG(w, NNHIP_EINVAL, "%s: null X / weights", fn);
+    const RecWeights rw = rec_from_lstm(w);
+    if (int rc = rec_common_checks(fn, X, &rw, 4, B, T, in, H, nl, rnl, 1)) return rc;
     NNHIP_CHECK_ARG(Y && gates && cell && hprev, NNHIP_EINVAL, "%s: null output / saved-state buffer", fn);
     NNHIP_CHECK_ARG(aligned4(h0) && aligned4(c0) && aligned4(Y) && aligned4(gates) && aligned4(cell) && aligned4(hprev) && aligned4(hT) &&
                         aligned4(cT), NNHIP_EALIGN, "%s: misaligned state / output buffer", fn);
     hipStream_t st = (hipStream_t)stream;
     const int Hp = (int)ceil_div(H, 16) * 16;
     const int64_t G = 4 * (int64_t)Hp;
-    int rc = 0;
-    float* ws = lstm_pack(w, in, (int)H, Hp, 0, st, &rc);
-    if (!ws) return rc;
+    float* ws = nullptr;                                        // wxp [in, 4Hp] | whp [Hp, 4Hp] | bp [4Hp]
+    int rc = rec_pack(&rw, 4, 1, in, (int)H, Hp, 0, st, &ws);
+    if (rc) return rc;
     // P = X W_x + b for all B*T rows and the four gates: one GEMM into the saved-gates buffer
     rc = gemm_f32(X, ws, gates, ws + (in + Hp) * G, nullptr, B * T, G, in, in, G, G, true, false, 1, 0, 0, 0, 0, 1.0f, st);
     if (rc) return rc;
@@ -406,55 +343,44 @@ extern "C" int nnhipLSTMForward(const float* X, const nnhipLSTMWeights* w, const
     a.gates = gates; a.whp = ws + in * G; a.h0 = h0; a.c0 = c0; a.Y = Y; a.cell = cell; a.hprev = hprev; a.hT = hT; a.cT = cT;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const dim3 blocks((unsigned)ceil_div(B, kLstmRows));
-    const size_t lds = (size_t)2 * kLstmRows * (Hp + 4) * sizeof(float);
+    const dim3 blocks((unsigned)ceil_div(B, kRecRows));
+    const size_t lds = (size_t)2 * kRecRows * (Hp + 4) * sizeof(float);
     if (Hp == 128 && lstm_resident_on()) return recurrence_run(lstm_fwd_kernel<true, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
-    if (Hp <= 128) return recurrence_run(lstm_fwd_kernel<false, 1>, a, blocks, lds, st, "lstm_fwd_kernel");
-    if (Hp <= 256) return recurrence_run(lstm_fwd_kernel<false, 2>, a, blocks, lds, st, "lstm_fwd_kernel");
-    return recurrence_run(lstm_fwd_kernel<false, 4>, a, blocks, lds, st, "lstm_fwd_kernel");
+    return rec_tiers(Hp, [&](auto mt) { return recurrence_run(lstm_fwd_kernel<false, decltype(mt)::value>, a, blocks, lds, st, "lstm_fwd_kernel"); });
 }
 
 extern "C" int nnhipLSTMBackward(const float* X, const nnhipLSTMWeights* w, const float* gates, const float* cell, const float* hprev,
                                  const float* dY, const float* dYlast, float* dX, const nnhipLSTMGrads* grads, int64_t B, int64_t T,
                                  int64_t in, int64_t H, int nl, int rnl, nnhipStream_t stream) {
     const char* fn = "nnhipLSTMBackward";
-    if (int rc = lstm_common_checks(fn, X, w, B, T, in, H, nl, rnl)) return rc;
+    NNHIP_CHECK_ARG(w, NNHIP_EINVAL, "%s: null X / weights", fn);
+    const RecWeights rw = rec_from_lstm(w);
+    if (int rc = rec_common_checks(fn, X, &rw, 4, B, T, in, H, nl, rnl, 1)) return rc;
     NNHIP_CHECK_ARG(gates && cell && hprev, NNHIP_EINVAL, "%s: null saved-state buffer", fn);
     NNHIP_CHECK_ARG(dY || dYlast, NNHIP_EINVAL, "%s: null dY and dYlast", fn);
     NNHIP_CHECK_ARG(aligned4(gates) && aligned4(cell) && aligned4(hprev) && aligned4(dY) && aligned4(dYlast) && aligned4(dX), NNHIP_EALIGN,
                     "%s: misaligned saved-state / gradient buffer", fn);
-    for (int g = 0; grads && g < 4; ++g)
-        NNHIP_CHECK_ARG(aligned4(grads->dwx[g]) && aligned4(grads->dwh[g]) && aligned4(grads->db[g]), NNHIP_EALIGN,
+    RecGrads rg;
+    for (int g = 0; grads && g < 4; ++g) {
+        rg.dwx[g] = grads->dwx[g]; rg.dwh[g] = grads->dwh[g]; rg.db[g] = grads->db[g];
+        NNHIP_CHECK_ARG(aligned4(rg.dwx[g]) && aligned4(rg.dwh[g]) && aligned4(rg.db[g]), NNHIP_EALIGN,
                         "%s: misaligned parameter gradient buffer", fn);
+    }
     hipStream_t st = (hipStream_t)stream;
     const int Hp = (int)ceil_div(H, 16) * 16;
     const int64_t G = 4 * (int64_t)Hp, BT = B * T;
-    int rc = 0;
-    float* ws = lstm_pack(w, in, (int)H, Hp, (size_t)(BT * G), st, &rc);
-    if (!ws) return rc;
-    const float* wxp = ws;
+    float* ws = nullptr;                                        // wxp | whp | bp | dG [B, T, 4Hp]
+    int rc = rec_pack(&rw, 4, 1, in, (int)H, Hp, (size_t)(BT * G), st, &ws);
+    if (rc) return rc;
     float* dG = ws + (in + Hp) * G + G;
     LstmBwdArgs a;
     a.gates = gates; a.cell = cell; a.whp = ws + in * G; a.dY = dY; a.dYlast = dYlast; a.dG = dG;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const dim3 blocks((unsigned)ceil_div(B, kLstmRows));
-    const size_t lds = (size_t)kLstmRows * (G + 4) * sizeof(float);
+    const dim3 blocks((unsigned)ceil_div(B, kRecRows));
+    const size_t lds = (size_t)kRecRows * (G + 4) * sizeof(float);
     if (Hp == 128 && lstm_resident_on()) rc = recurrence_run(lstm_bwd_kernel<true, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else if (Hp <= 128) rc = recurrence_run(lstm_bwd_kernel<false, 1>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else if (Hp <= 256) rc = recurrence_run(lstm_bwd_kernel<false, 2>, a, blocks, lds, st, "lstm_bwd_kernel");
-    else rc = recurrence_run(lstm_bwd_kernel<false, 4>, a, blocks, lds, st, "lstm_bwd_kernel");
+    else rc = rec_tiers(Hp, [&](auto mt) { return recurrence_run(lstm_bwd_kernel<false, decltype(mt)::value>, a, blocks, lds, st, "lstm_bwd_kernel"); });
     if (rc) return rc;
-    // time-parallel part: whole-sequence GEMMs straight into the caller's gradient buffers
-    if (dX && (rc = gemm_f32(dG, wxp, dX, nullptr, nullptr, BT, in, G, G, G, in, true, true, 1, 0, 0, 0, 0, 1.0f, st))) return rc;
-    if (!grads) return 0;
-    for (int g = 0; g < 4; ++g) {
-        const float* dGg = dG + (int64_t)g * Hp;
-        if (grads->dwx[g] && (rc = gemm_f32(X, dGg, grads->dwx[g], nullptr, nullptr, in, H, BT, in, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
-            return rc;
-        if (grads->dwh[g] && (rc = gemm_f32(hprev, dGg, grads->dwh[g], nullptr, nullptr, H, H, BT, H, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
-            return rc;
-        if (grads->db[g] && (rc = colsum(dGg, BT, H, G, grads->db[g], st))) return rc;
-    }
-    return 0;
+    return rec_bwd_epilogue(X, ws, dG, hprev, nullptr, 0, dX, nullptr, grads ? &rg : nullptr, 4, 1, B, T, in, H, Hp, st);
 }

@@ -20,17 +20,6 @@
 
 namespace nnhip {
 
-struct RecWeights {          // one direction, gate order z, r, h (GRU) or the single gate (RNN)
-    const float* wx[3];
-    const float* wh[3];
-    const float* b[3];
-};
-struct RecGrads {
-    float* dwx[3];
-    float* dwh[3];
-    float* db[3];
-};
-
 struct RecPack {
     RecWeights w[2];
     float* base;            // direction d at base + d * stride: wxp [in, G] | whp [Hp, G] | bp [G]
@@ -137,33 +126,26 @@ struct RecFwdArgs {
 //                phase B  c = nl(P_h + (r * h_{t-1}) W_hh);  h_t = z h_{t-1} + (1 - z) c -> the other h buffer;  barrier.
 // NG == 1 (RNN): phase B alone with h_{t-1} as its operand:  h_t = nl(P + h_{t-1} W_h).
 template <int NG, int MAXT>
-__global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdArgs a) {
+__global__ __launch_bounds__(kRecThreads, 1) void rec_fwd_kernel(const RecFwdArgs a) {
     extern __shared__ float lds[];
     const int Hp = a.Hp, ldh = Hp + 4, G = NG * Hp, KS = Hp / 4, ntile = Hp / 16;
-    if (Hp > MAXT * 16 * kLstmWaves || blockDim.x != kLstmThreads) {
-        // impossible by the host's dispatch: leave the outputs alone and raise the library's device error word
-        if (threadIdx.x == 0 && a.err) __hip_atomic_store(a.err, (unsigned)NNHIP_DEVERR_RECURRENT_SHAPE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
+    if (rec_bad_shape<MAXT>(Hp, a.err, NNHIP_DEVERR_RECURRENT_SHAPE)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, col = lane & 15;
-    const int b0 = blockIdx.x * kLstmRows, dir = blockIdx.y;
+    const int b0 = blockIdx.x * kRecRows, dir = blockIdx.y;
     const int64_t BT = (int64_t)a.B * a.T, BH = (int64_t)a.B * a.H;
     float* gates = a.gates + dir * BT * G;
     const float* whp = a.wp + dir * a.wstride + a.in * G;
     const float* h0 = a.h0 ? a.h0 + dir * BH : nullptr;
     float* Y = a.Y + dir * BT * a.H;
     float* hprev = a.hprev + dir * BT * a.H;
-    float* hbuf[2] = {lds, lds + kLstmRows * ldh};
-    float* rh = lds + 2 * kLstmRows * ldh;                            // NG == 3 only
+    float* hbuf[2] = {lds, lds + kRecRows * ldh};
+    float* rh = lds + 2 * kRecRows * ldh;                            // NG == 3 only
 
-    for (int idx = threadIdx.x; idx < kLstmRows * Hp; idx += kLstmThreads) {
-        const int r = idx / Hp, j = idx - r * Hp, b = b0 + r;
-        hbuf[0][r * ldh + j] = (h0 && b < a.B && j < a.H) ? h0[(int64_t)b * a.H + j] : 0.0f;
-    }
+    rec_stage_state(h0, a.B, a.H, Hp, ldh, b0, hbuf[0]);
     float hreg[MAXT][4];
 #pragma unroll
     for (int tt = 0; tt < MAXT; ++tt) {
-        const int j = (wave + tt * kLstmWaves) * 16 + col;
+        const int j = (wave + tt * kRecWaves) * 16 + col;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int b = b0 + q * 4 + r;
@@ -179,7 +161,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdAr
         float zreg[MAXT][4], ph[MAXT][4];
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile) {                                         // wave-uniform
                 const int j = jt * 16 + col;
                 float pre[NG == 3 ? 2 : 1][4];
@@ -199,8 +181,8 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdAr
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = q * 4 + r, b = b0 + row;
-                        const float z = lstm_act(a.rnl, acc[0][r] + pre[0][r]);
-                        const float rr = lstm_act(a.rnl, acc[1][r] + pre[1][r]);
+                        const float z = rec_act(a.rnl, acc[0][r] + pre[0][r]);
+                        const float rr = rec_act(a.rnl, acc[1][r] + pre[1][r]);
                         zreg[tt][r] = z;
                         rh[row * ldh + j] = rr * hreg[tt][r];
                         if (b < a.B) {
@@ -215,7 +197,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdAr
         if constexpr (NG == 3) __syncthreads();                       // r * h_{t-1} is complete
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile) {
                 const int j = jt * 16 + col;
                 f32x4_ acc[1] = {f32x4_{0.f, 0.f, 0.f, 0.f}};
@@ -223,7 +205,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdAr
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = q * 4 + r, b = b0 + row;
-                    const float c = lstm_act(a.nl, acc[0][r] + ph[tt][r]);
+                    const float c = rec_act(a.nl, acc[0][r] + ph[tt][r]);
                     float h = c;
                     if constexpr (NG == 3) {
                         h = zreg[tt][r] * hreg[tt][r] + (1.0f - zreg[tt][r]) * c;
@@ -245,7 +227,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_fwd_kernel(const RecFwdAr
         float* hT = a.hT + dir * BH;
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int j = (wave + tt * kLstmWaves) * 16 + col;
+            const int j = (wave + tt * kRecWaves) * 16 + col;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int b = b0 + q * 4 + r;
@@ -276,15 +258,12 @@ struct RecBwdArgs {
 // NG == 1 (rnn.py:46-56):   ds = hd nl'(h_t) -> LDS;  barrier;  carry = ds W_h^T;  barrier.
 // The MFMA outputs have the forward's (row, column) ownership, so a lane's saved values are those of its own accumulator elements.
 template <int NG, int MAXT>
-__global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdArgs a) {
+__global__ __launch_bounds__(kRecThreads, 1) void rec_bwd_kernel(const RecBwdArgs a) {
     extern __shared__ float lds[];
     const int Hp = a.Hp, G = NG * Hp, ldc = Hp + 4, ldz = 2 * Hp + 4, ntile = Hp / 16;
-    if (Hp > MAXT * 16 * kLstmWaves || blockDim.x != kLstmThreads) {
-        if (threadIdx.x == 0 && a.err) __hip_atomic_store(a.err, (unsigned)NNHIP_DEVERR_RECURRENT_SHAPE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
+    if (rec_bad_shape<MAXT>(Hp, a.err, NNHIP_DEVERR_RECURRENT_SHAPE)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, col = lane & 15;
-    const int b0 = blockIdx.x * kLstmRows, dir = blockIdx.y;
+    const int b0 = blockIdx.x * kRecRows, dir = blockIdx.y;
     const int64_t BT = (int64_t)a.B * a.T;
     const float* gates = a.gates + dir * BT * (NG == 3 ? G : a.H);
     const float* hprev = a.hprev + dir * BT * a.H;
@@ -294,7 +273,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
     float* dG = a.dG + dir * BT * G;
     float* rh = NG == 3 ? a.rh + dir * a.rhstride : nullptr;
     float* dcb = lds;                                                 // 16 x (Hp + 4): dc_t (RNN: ds_t)
-    float* dzr = lds + kLstmRows * ldc;                               // 16 x (2Hp + 4): dz_t | dr_t (NG == 3 only)
+    float* dzr = lds + kRecRows * ldc;                               // 16 x (2Hp + 4): dz_t | dr_t (NG == 3 only)
 
     float carry[MAXT][4];
 #pragma unroll
@@ -307,7 +286,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
         float hdz[MAXT][4], rv[MAXT][4], fr[MAXT][4], dz[MAXT][4];    // what phase B needs of this lane's elements (NG == 3)
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile) {                                         // wave-uniform
                 const int j = jt * 16 + col;
 #pragma unroll
@@ -323,15 +302,15 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
                         const float* gp = gates + bt * G + j;
                         const float z = v ? gp[0] : 0.0f, rr = v ? gp[Hp] : 0.0f, c = v ? gp[2 * Hp] : 0.0f;
                         const float hp = v ? hprev[bt * a.H + j] : 0.0f;
-                        dc = v ? hd * (1.0f - z) * lstm_dact_y(a.nl, c) : 0.0f;
-                        dz[tt][r] = v ? hd * (hp - c) * lstm_dact_y(a.rnl, z) : 0.0f;
-                        fr[tt][r] = hp * lstm_dact_y(a.rnl, rr);
+                        dc = v ? hd * (1.0f - z) * rec_dact_y(a.nl, c) : 0.0f;
+                        dz[tt][r] = v ? hd * (hp - c) * rec_dact_y(a.rnl, z) : 0.0f;
+                        fr[tt][r] = hp * rec_dact_y(a.rnl, rr);
                         hdz[tt][r] = hd * z;
                         rv[tt][r] = rr;
                         if (v) rh[bt * a.H + j] = rr * hp;
                     } else {
                         const float h = v ? gates[bs * a.H + j] : 0.0f;
-                        dc = v ? hd * lstm_dact_y(a.nl, h) : 0.0f;
+                        dc = v ? hd * rec_dact_y(a.nl, h) : 0.0f;
                     }
                     dcb[row * ldc + j] = dc;
                     if (b < a.B) dG[bt * G + (NG - 1) * Hp + j] = dc;
@@ -343,7 +322,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
 #pragma unroll
         for (int tt = 0; tt < MAXT; ++tt) {
             tmp[tt] = f32x4_{0.f, 0.f, 0.f, 0.f};
-            const int jt = wave + tt * kLstmWaves;
+            const int jt = wave + tt * kRecWaves;
             if (jt < ntile && (NG == 3 || s > 0))                     // the RNN's product only feeds the next step's carry
                 tmp[tt] = rec_mfma_rows(dcb + col * ldc + q * (Hp / 4), whp + (int64_t)(jt * 16 + col) * G + (NG - 1) * Hp + q * (Hp / 4), Hp / 4,
                                         tmp[tt]);
@@ -351,7 +330,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
         if constexpr (NG == 3) {
 #pragma unroll
             for (int tt = 0; tt < MAXT; ++tt) {
-                const int jt = wave + tt * kLstmWaves;
+                const int jt = wave + tt * kRecWaves;
                 if (jt < ntile) {
                     const int j = jt * 16 + col;
 #pragma unroll
@@ -372,7 +351,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
             __syncthreads();                                          // dz_t | dr_t is complete
 #pragma unroll
             for (int tt = 0; tt < MAXT; ++tt) {
-                const int jt = wave + tt * kLstmWaves;
+                const int jt = wave + tt * kRecWaves;
                 if (jt < ntile) {
                     const int j = jt * 16 + col;
                     f32x4_ acc = f32x4_{0.f, 0.f, 0.f, 0.f};
@@ -390,7 +369,7 @@ __global__ __launch_bounds__(kLstmThreads, 1) void rec_bwd_kernel(const RecBwdAr
             for (int tt = 0; tt < MAXT; ++tt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const bool v = b0 + q * 4 + r < a.B && (wave + tt * kLstmWaves) * 16 + col < a.H;
+                    const bool v = b0 + q * 4 + r < a.B && (wave + tt * kRecWaves) * 16 + col < a.H;
                     carry[tt][r] = v ? tmp[tt][r] : 0.0f;
                 }
             __syncthreads();                                          // every wave is done reading ds_t
@@ -452,13 +431,13 @@ __global__ __launch_bounds__(256) void bidir_merge_bwd_kernel(const MergeArgs a)
 
 static int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
-static int rec_common_checks(const char* fn, const float* X, const RecWeights* w, int ng, int64_t B, int64_t T, int64_t in, int64_t H, int nl,
-                             int rnl, int ndir) {
+int rec_common_checks(const char* fn, const float* X, const RecWeights* w, int ng, int64_t B, int64_t T, int64_t in, int64_t H, int nl,
+                      int rnl, int ndir) {
     NNHIP_CHECK_ARG(B >= 1 && T >= 1 && in >= 1 && H >= 1, NNHIP_EINVAL, "%s: sizes must be positive (B %lld, T %lld, in %lld, H %lld)", fn,
                     (long long)B, (long long)T, (long long)in, (long long)H);
     NNHIP_CHECK_ARG(ndir == 1 || ndir == 2, NNHIP_EINVAL, "%s: ndir must be 1 or 2, got %d", fn, ndir);
-    NNHIP_CHECK_ARG(H <= kLstmMaxH, NNHIP_EINVAL, "%s: hidden_size %lld > %d is not supported", fn, (long long)H, kLstmMaxH);
-    NNHIP_CHECK_ARG(B * T < ((int64_t)1 << 30) && in < ((int64_t)1 << 31), NNHIP_EINVAL, "%s: B*T or in_features too large", fn);
+    NNHIP_CHECK_ARG(H <= kRecMaxH, NNHIP_EINVAL, "%s: hidden_size %lld > %d is not supported", fn, (long long)H, kRecMaxH);
+    NNHIP_CHECK_ARG(ndir * B * T < ((int64_t)1 << 31) && in < ((int64_t)1 << 31), NNHIP_EINVAL, "%s: B*T or in_features too large", fn);
     NNHIP_CHECK_ARG(nl >= 0 && nl <= 2 && rnl >= 0 && rnl <= 2, NNHIP_EINVAL, "%s: bad nonlinearity code (%d, %d)", fn, nl, rnl);
     NNHIP_CHECK_ARG(X, NNHIP_EINVAL, "%s: null X / weights", fn);
     for (int d = 0; d < ndir; ++d)
@@ -470,8 +449,7 @@ static int rec_common_checks(const char* fn, const float* X, const RecWeights* w
     return 0;
 }
 
-// packs the parameters of every direction into arena 2; *out = its base: ndir x (wxp [in, G] | whp [Hp, G] | bp [G]) | extra floats
-static int rec_pack(const RecWeights* w, int ng, int ndir, int64_t in, int H, int Hp, size_t extra, hipStream_t st, float** out) {
+int rec_pack(const RecWeights* w, int ng, int ndir, int64_t in, int H, int Hp, size_t extra, hipStream_t st, float** out) {
     const int64_t G = (int64_t)ng * Hp, n = (in + Hp) * G + G;
     float* ws = static_cast<float*>(workspace_arena(2, (size_t)(ndir * n + extra) * sizeof(float)));
     if (!ws) {
@@ -489,18 +467,33 @@ static int rec_pack(const RecWeights* w, int ng, int ndir, int64_t in, int H, in
     return 0;
 }
 
-// tiers as the LSTM's: 1 / 2 / 4 hidden tiles per wave for Hp <= 128 / 256 / 512.  No register-resident W_h tier (not measured).
-template <int NG>
-static int rec_run_fwd(const RecFwdArgs& a, dim3 blocks, size_t lds, hipStream_t st) {
-    if (a.Hp <= 128) return recurrence_run(rec_fwd_kernel<NG, 1>, a, blocks, lds, st, "rec_fwd_kernel");
-    if (a.Hp <= 256) return recurrence_run(rec_fwd_kernel<NG, 2>, a, blocks, lds, st, "rec_fwd_kernel");
-    return recurrence_run(rec_fwd_kernel<NG, 4>, a, blocks, lds, st, "rec_fwd_kernel");
-}
-template <int NG>
-static int rec_run_bwd(const RecBwdArgs& a, dim3 blocks, size_t lds, hipStream_t st) {
-    if (a.Hp <= 128) return recurrence_run(rec_bwd_kernel<NG, 1>, a, blocks, lds, st, "rec_bwd_kernel");
-    if (a.Hp <= 256) return recurrence_run(rec_bwd_kernel<NG, 2>, a, blocks, lds, st, "rec_bwd_kernel");
-    return recurrence_run(rec_bwd_kernel<NG, 4>, a, blocks, lds, st, "rec_bwd_kernel");
+int rec_bwd_epilogue(const float* X, const float* ws, const float* dG, const float* hprev, const float* last_left, int64_t last_stride,
+                     float* dX, float* dX1, const RecGrads* grads, int ng, int ndir, int64_t B, int64_t T, int64_t in, int64_t H, int Hp,
+                     hipStream_t st) {
+    const int64_t G = (int64_t)ng * Hp, BT = B * T, stride = (in + Hp) * G + G;
+    int rc = 0;
+    for (int d = 0; dX && d < ndir; ++d) {
+        if ((rc = gemm_f32(dG + d * BT * G, ws + d * stride, d ? dX1 : dX, nullptr, nullptr, BT, in, G, G, G, in, true, true, 1, 0, 0, 0, 0, 1.0f, st)))
+            return rc;
+        if (d) {
+            const int64_t n = BT * in;
+            hipLaunchKernelGGL(rec_add_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0, st, dX, dX1, n);
+            NNHIP_LAUNCH_CHECK("rec_add_kernel");
+        }
+    }
+    for (int d = 0; grads && d < ndir; ++d) {
+        const float* hp = hprev + d * BT * H;
+        for (int g = 0; g < ng; ++g) {
+            const float* dGg = dG + d * BT * G + (int64_t)g * Hp;
+            const float* left = (last_left && g == ng - 1) ? last_left + d * last_stride : hp;
+            if (grads[d].dwx[g] && (rc = gemm_f32(X, dGg, grads[d].dwx[g], nullptr, nullptr, in, H, BT, in, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
+                return rc;
+            if (grads[d].dwh[g] && (rc = gemm_f32(left, dGg, grads[d].dwh[g], nullptr, nullptr, H, H, BT, H, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
+                return rc;
+            if (grads[d].db[g] && (rc = colsum(dGg, BT, H, G, grads[d].db[g], st))) return rc;
+        }
+    }
+    return 0;
 }
 
 // gates: GRU the caller's saved-gates buffer [ndir, B, T, 3Hp]; RNN NULL (P lives in the workspace: the activated value is Y itself)
@@ -527,9 +520,10 @@ static int rec_forward(const char* fn, const float* X, const RecWeights* w, cons
     a.gates = P; a.wp = ws; a.wstride = stride; a.in = in; a.h0 = h0; a.Y = Y; a.hprev = hprev; a.hT = hT;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const dim3 blocks((unsigned)ceil_div(B, kLstmRows), (unsigned)ndir);
-    const size_t lds = (size_t)(NG == 3 ? 3 : 2) * kLstmRows * (Hp + 4) * sizeof(float);
-    return rec_run_fwd<NG>(a, blocks, lds, st);
+    const dim3 blocks((unsigned)ceil_div(B, kRecRows), (unsigned)ndir);
+    const size_t lds = (size_t)(NG == 3 ? 3 : 2) * kRecRows * (Hp + 4) * sizeof(float);
+    // no register-resident W_h tier (not measured)
+    return rec_tiers(Hp, [&](auto mt) { return recurrence_run(rec_fwd_kernel<NG, decltype(mt)::value>, a, blocks, lds, st, "rec_fwd_kernel"); });
 }
 
 template <int NG>
@@ -559,41 +553,18 @@ static int rec_backward(const char* fn, const float* X, const RecWeights* w, con
     a.rhstride = rhstride;
     a.err = device_error_word();
     a.B = (int)B; a.T = (int)T; a.H = (int)H; a.Hp = Hp; a.nl = nl; a.rnl = rnl;
-    const dim3 blocks((unsigned)ceil_div(B, kLstmRows), (unsigned)ndir);
-    const size_t lds = (size_t)kLstmRows * (NG == 3 ? 3 * Hp + 8 : Hp + 4) * sizeof(float);
-    if ((rc = rec_run_bwd<NG>(a, blocks, lds, st))) return rc;
-    // time-parallel part: whole-sequence GEMMs straight into the caller's gradient buffers.  dG of both directions is in input order,
-    // so dX is the sum of the two products; the second goes through the workspace and one elementwise add.
-    for (int d = 0; dX && d < ndir; ++d) {
-        if ((rc = gemm_f32(dG + d * BT * G, ws + d * stride, d ? dX1 : dX, nullptr, nullptr, BT, in, G, G, G, in, true, true, 1, 0, 0, 0, 0, 1.0f, st)))
-            return rc;
-        if (d) {
-            const int64_t n = BT * in;
-            hipLaunchKernelGGL(rec_add_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0, st, dX, dX1, n);
-            NNHIP_LAUNCH_CHECK("rec_add_kernel");
-        }
-    }
-    for (int d = 0; grads && d < ndir; ++d) {
-        const float* hp = hprev + d * BT * H;
-        for (int g = 0; g < NG; ++g) {
-            const float* dGg = dG + d * BT * G + (int64_t)g * Hp;
-            const float* left = (NG == 3 && g == 2) ? rh + d * rhstride : hp;       // dW_hh = (r * H_prev)^T dc
-            if (grads[d].dwx[g] && (rc = gemm_f32(X, dGg, grads[d].dwx[g], nullptr, nullptr, in, H, BT, in, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
-                return rc;
-            if (grads[d].dwh[g] && (rc = gemm_f32(left, dGg, grads[d].dwh[g], nullptr, nullptr, H, H, BT, H, G, H, false, false, 1, 0, 0, 0, 0, 1.0f, st)))
-                return rc;
-            if (grads[d].db[g] && (rc = colsum(dGg, BT, H, G, grads[d].db[g], st))) return rc;
-        }
-    }
-    return 0;
+    const dim3 blocks((unsigned)ceil_div(B, kRecRows), (unsigned)ndir);
+    const size_t lds = (size_t)kRecRows * (NG == 3 ? 3 * Hp + 8 : Hp + 4) * sizeof(float);
+    rc = rec_tiers(Hp, [&](auto mt) { return recurrence_run(rec_bwd_kernel<NG, decltype(mt)::value>, a, blocks, lds, st, "rec_bwd_kernel"); });
+    if (rc) return rc;
+    return rec_bwd_epilogue(X, ws, dG, hprev, NG == 3 ? rh : nullptr, rhstride, dX, dX1, grads, NG, ndir, B, T, in, H, Hp, st);
 }
 
 static void rec_from_gru(const nnhipGRUWeights* w, int ndir, RecWeights (&out)[2]) {
-    for (int d = 0; d < 2; ++d)
-        for (int g = 0; g < 3; ++g) {
-            const nnhipGRUWeights& s = w[d < ndir ? d : 0];
-            out[d].wx[g] = s.wx[g]; out[d].wh[g] = s.wh[g]; out[d].b[g] = s.b[g];
-        }
+    for (int d = 0; d < 2; ++d) {
+        const nnhipGRUWeights& s = w[d < ndir ? d : 0];
+        out[d] = RecWeights{{s.wx[0], s.wx[1], s.wx[2]}, {s.wh[0], s.wh[1], s.wh[2]}, {s.b[0], s.b[1], s.b[2]}};
+    }
 }
 static void rec_from_rnn(const nnhipRNNWeights* w, int ndir, RecWeights (&out)[2]) {
     for (int d = 0; d < 2; ++d) {

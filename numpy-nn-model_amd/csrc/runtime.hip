@@ -27,10 +27,11 @@ static std::mutex g_ws_mu;
 // Two grow-only blocks: 0 = the general workspace (split-K slabs, column-sum partials, ...), 1 = the slabs of the GROUPED parameter-
 // gradient launch (gemm.hip: gemm_f32_wgrad_group) -- its own block because that launch may run on a side stream next to kernels of
 // the main stream that use block 0 (neunet_hip/_lib.py: NNHIP_WGRAD_STREAM; round 6).
-// 2 = the LSTM entries' scratch (packed gate weights, dG): those entries call the GEMM and column-sum kernels, which take block 0,
-// while their own scratch is live (recurrent.hip; ABI 211).  nnhipConvTranspose2dBackward keeps its mirrored weight gradient there
-// for the same reason: conv_mfma_wgrad's slabs take block 0 while it is written (conv_transpose.hip; ABI 216).  Both users are
-// ordered by the caller's stream and never hold the block across calls.
+// 2 = the recurrent entries' scratch (packed gate weights, dG, ...): the LSTM, GRU and RNN entries call the GEMM and column-sum
+// kernels, which take block 0, while their own scratch is live (rec_pack in recurrent_gru.hip, declared in recurrent_common.h; ABI
+// 211 / 220).  nnhipConvTranspose2dBackward keeps its mirrored weight gradient there for the same reason: conv_mfma_wgrad's slabs
+// take block 0 while it is written (conv_transpose.hip; ABI 216).  All users are ordered by the caller's stream and never hold the
+// block across calls.
 static void* g_ws[3] = {nullptr, nullptr, nullptr};
 static size_t g_ws_bytes[3] = {0, 0, 0};
 static bool g_ws_locked = false;   // nnhipWorkspaceLock: a captured hipGraph holds the blocks' addresses

@@ -1,12 +1,13 @@
 """HIPLSTM, HIPGRU, HIPRNN, HIPBidirectional -- the recurrent layers on the one-launch recurrence kernels (csrc/recurrent.hip, ABI 211;
-csrc/recurrent_gru.hip, ABI 220; net-new: the reference has no CUDA recurrences).  The LSTM first; GRU / RNN / Bidirectional below it.
-CPU semantics: neunet/nn/layers/lstm.py -- parameters :187-247, forward :254-408, backward (BPTT) :16-143, nonlinearities :412-460.
+csrc/recurrent_gru.hip, ABI 220; net-new: the reference has no CUDA recurrences).  One set of helpers and one base class serve the
+three layers; a layer adds its parameters and whatever of its checks differs.
+CPU semantics: neunet/nn/layers/lstm.py -- parameters :187-247, forward :254-408, backward (BPTT) :16-143, nonlinearities :412-460;
+gru.py, rnn.py and bidirectional.py as cited below.
 
-A layer's forward is the input projection P = X W_x + b (one GEMM over all B*T rows and the four gates) followed by ONE launch that
-runs every timestep; the backward is one launch for the recurrence followed by whole-sequence GEMMs for dX and the twelve parameter
+A layer's forward is the input projection P = X W_x + b (one GEMM over all B*T rows and every gate) followed by ONE launch that
+runs every timestep; the backward is one launch for the recurrence followed by whole-sequence GEMMs for dX and the parameter
 gradients.  Whatever T is, a layer costs a fixed handful of launches."""
 import copy
-import ctypes
 from typing import Union
 
 import numpy as np
@@ -26,156 +27,15 @@ def _padded(h):
     return (h + 15) // 16 * 16
 
 
-def _weights_struct(params):
-    w = LSTMWeights()
-    for g in range(4):
-        w.wx[g] = params[g].data.data_ptr()
-        w.wh[g] = params[4 + g].data.data_ptr()
-        w.b[g] = params[8 + g].data.data_ptr()
-    return w
-
-
 def _array(v):
     if v is None:
         return None
     return v.data if isinstance(v, Tensor) else v
 
 
-class _HIPLSTMTensor(Tensor):
-    """One output of HIPLSTM.  `which` is "all" (the gradient of every h_t) or "last" (the gradient of h_{T-1} alone); each output has
-    its own BPTT grad_fn, as in the reference (lstm.py:400-408) -- with return_sequences="both" the two passes add up in X and the
-    parameters because the gradient is linear."""
-
-    def __init__(self, data, args, device, saved, which):
-        super().__init__(data, args, "lstm", device=device, _nocopy=True)
-
-        def grad_fn(X, *params, grad):
-            s = saved
-            B, T, n_in, H = s["B"], s["T"], s["in"], s["H"]
-            grad = grad if grad.is_contiguous() else grad.contiguous()
-            dY, dYlast = (grad, None) if which == "all" else (None, grad)
-            dX = X.xp.empty((B, T, n_in), dtype=np.float32) if X.requires_grad else None
-            outs = [_grad_out(p, p.data) for p in params]
-            g = LSTMGrads()
-            for k in range(4):
-                g.dwx[k] = outs[k].data_ptr()
-                g.dwh[k] = outs[4 + k].data_ptr()
-                g.db[k] = outs[8 + k].data_ptr()
-            call_hip_function("nnhipLSTMBackward", s["X"], ctypes.byref(_weights_struct(params)), s["gates"], s["cell"], s["hprev"],
-                              dY, dYlast, dX, ctypes.byref(g), B, T, n_in, H, s["nl"], s["rnl"], get_current_stream_ptr())
-            if dX is not None:
-                X.apply_grad(dX.reshape(X.shape))
-            for p, o in zip(params, outs):
-                _finish_param(p, o)
-
-        self.grad_fn = grad_fn
-
-
-class HIPLSTM(Module):
-    """neunet.nn.LSTM (lstm.py:168-252).  Differences from the reference, both deliberate:
-      * bias=False raises: the reference's `a + b + bias if bias is not None else +0` (lstm.py:313-319) parses as
-        `(a + b + bias) if ... else 0`, so without a bias every pre-activation is 0 and the layer outputs zeros whatever the input;
-      * with cycled_states the carried (h, c) live in module-owned device buffers that the kernel itself rewrites, so a replayed
-        hipGraph carries them from replay to replay exactly as eager calls do.  Their shape is (batch, hidden)."""
-
-    def __init__(self, input_size: int, hidden_size: int, nonlinearity: str = "tanh", recurrent_nonlinearity: str = "sigmoid",
-                 return_sequences: Union[str, bool] = "both", bias: bool = True, cycled_states: bool = False, device="cuda"):
-        super().__init__()
-        for name in (nonlinearity, recurrent_nonlinearity):
-            if name not in NONLINEARITIES:
-                raise ValueError(f"unknown nonlinearity {name!r}: one of {sorted(NONLINEARITIES)} (lstm.py:460)")
-        if not bias:
-            raise ValueError("LSTM(bias=False) is not supported: in the reference it outputs zeros whatever the input "
-                             "(neunet/nn/layers/lstm.py:318 -- the conditional expression drops the whole pre-activation)")
-        if return_sequences not in ("both", "all", "last", True, False):
-            raise ValueError(f"return_sequences must be 'both', 'all', 'last', True or False, got {return_sequences!r}")
-        self.input_size, self.hidden_size = input_size, hidden_size
-        self.nonlinearity, self.recurrent_nonlinearity = nonlinearity, recurrent_nonlinearity
-        self.return_sequences, self.cycled_states = return_sequences, cycled_states
-        stdv = 1.0 / np.sqrt(hidden_size)
-        # drawn from the global generator in the reference's order and dtype (float64 draws, stored as float32; lstm.py:187-242)
-        self.weight_f = Parameter(Tensor(np.random.uniform(-stdv, stdv, (input_size, hidden_size)), dtype=np.float32))
-        self.weight_i = Parameter(Tensor(np.random.uniform(-stdv, stdv, (input_size, hidden_size)), dtype=np.float32))
-        self.weight_o = Parameter(Tensor(np.random.uniform(-stdv, stdv, (input_size, hidden_size)), dtype=np.float32))
-        self.weight_c = Parameter(Tensor(np.random.uniform(-stdv, stdv, (input_size, hidden_size)), dtype=np.float32))
-        self.weight_hf = Parameter(Tensor(np.random.uniform(-stdv, stdv, (hidden_size, hidden_size)), dtype=np.float32))
-        self.weight_hi = Parameter(Tensor(np.random.uniform(-stdv, stdv, (hidden_size, hidden_size)), dtype=np.float32))
-        self.weight_ho = Parameter(Tensor(np.random.uniform(-stdv, stdv, (hidden_size, hidden_size)), dtype=np.float32))
-        self.weight_hc = Parameter(Tensor(np.random.uniform(-stdv, stdv, (hidden_size, hidden_size)), dtype=np.float32))
-        self.bias_f = Parameter(Tensor(np.zeros(hidden_size), dtype=np.float32))
-        self.bias_i = Parameter(Tensor(np.zeros(hidden_size), dtype=np.float32))
-        self.bias_o = Parameter(Tensor(np.zeros(hidden_size), dtype=np.float32))
-        self.bias_c = Parameter(Tensor(np.zeros(hidden_size), dtype=np.float32))
-        self.cprev = None
-        self.hprev = None
-        self.to(device)
-
-    def _params(self):
-        return [self.weight_f, self.weight_i, self.weight_o, self.weight_c, self.weight_hf, self.weight_hi, self.weight_ho,
-                self.weight_hc, self.bias_f, self.bias_i, self.bias_o, self.bias_c]
-
-    def forward(self, X: Tensor, hprev=None, cprev=None):
-        import torch
-        if not isinstance(X, Tensor):
-            raise TypeError("Input must be a tensor")
-        if X.device != self.device:
-            raise ValueError("Tensors must be on the same device")
-        require_device_f32(X)
-        if X.ndim not in (2, 3):
-            raise ValueError("LSTM expects a (batch, timesteps, input_size) or (timesteps, input_size) input")
-        if self.hidden_size > MAX_HIDDEN:
-            raise ValueError(f"hidden_size {self.hidden_size} > {MAX_HIDDEN} is not supported by the HIP recurrence kernels")
-        x = X.data if X.data.is_contiguous() else X.data.contiguous()
-        if X.ndim == 2:                                         # lstm.py:262-263: a single sequence is batch 1
-            x = x.reshape(1, *x.shape)
-        B, T, n_in = x.shape
-        H = self.hidden_size
-        if not self.cycled_states:
-            self.hprev, self.cprev = _array(hprev), _array(cprev)
-        if self.hprev is not None and tuple(self.hprev.shape) != (B, H):
-            raise ValueError("hprev shape must be equal to (batch_size, 1, hidden_size)")
-        if self.cprev is not None and tuple(self.cprev.shape) != (B, H):
-            raise ValueError("cprev shape must be equal to (batch_size, 1, hidden_size)")
-        if self.input_size != n_in:
-            raise ValueError("input_size must be equal to input shape[2]")
-        if self.cycled_states:
-            if self.hprev is None:
-                self.hprev = torch.zeros((B, H), dtype=torch.float32, device="cuda")
-            if self.cprev is None:
-                self.cprev = torch.zeros((B, H), dtype=torch.float32, device="cuda")
-        h0 = None if self.hprev is None else self.hprev.contiguous().to(torch.float32)
-        c0 = None if self.cprev is None else self.cprev.contiguous().to(torch.float32)
-        Hp = _padded(H)
-        Y = torch.empty((B, T, H), dtype=torch.float32, device="cuda")
-        gates = torch.empty((B, T, 4 * Hp), dtype=torch.float32, device="cuda")
-        cell = torch.empty((B, T + 1, H), dtype=torch.float32, device="cuda")
-        hprev_s = torch.empty((B, T, H), dtype=torch.float32, device="cuda")
-        last = torch.empty((B, 1, H), dtype=torch.float32, device="cuda")
-        # cycled: the kernel reads the state buffers and writes the new state into the same buffers (each element by its owner thread)
-        hT = self.hprev if self.cycled_states else last
-        cT = self.cprev if self.cycled_states else None
-        params = self._params()
-        nl, rnl = NONLINEARITIES[self.nonlinearity], NONLINEARITIES[self.recurrent_nonlinearity]
-        call_hip_function("nnhipLSTMForward", x, ctypes.byref(_weights_struct(params)), h0, c0, Y, gates, cell, hprev_s, hT, cT,
-                          B, T, n_in, H, nl, rnl, get_current_stream_ptr())
-        if self.cycled_states:
-            last.copy_(self.hprev.reshape(B, 1, H))
-        saved = dict(X=x, gates=gates, cell=cell, hprev=hprev_s, B=B, T=T, H=H, nl=nl, rnl=rnl, **{"in": n_in})
-        args = (X, *params)
-        rs = self.return_sequences
-        if rs in ("all", True) and rs is not False:
-            return _HIPLSTMTensor(Y, args, self.device, saved, "all")
-        if rs in ("last", False):
-            return _HIPLSTMTensor(last, args, self.device, saved, "last")
-        return _HIPLSTMTensor(Y, args, self.device, saved, "all"), _HIPLSTMTensor(last, args, self.device, saved, "last")
-
-    def __call__(self, X, hprev=None, cprev=None):
-        return self.forward(X, hprev, cprev)
-
-
-# ---------------------------------------------------------------------------------------------- GRU / RNN / Bidirectional (ABI 220)
 MERGE_MODES = {"concat": 0, "sum": 1, "mul": 2, "avg": 3}  # include/neunet_hip.h: NNHIP_MERGE_*
 _RS = ("both", "all", "last", True, False)
+_STRUCTS = {"lstm": (LSTMWeights, LSTMGrads, 4), "gru": (GRUWeights, GRUGrads, 3), "rnn": (RNNWeights, RNNGrads, 1)}   # + gate count
 
 
 def _check_return_sequences(rs):
@@ -186,16 +46,15 @@ def _check_return_sequences(rs):
 def _rec_structs(layers, outs=None):
     """The ndir weight structs of `layers` (one layer, or the direct and the reverse layer of a Bidirectional) and, with `outs` (one
     list of gradient buffers per layer), the gradient structs."""
-    gru = layers[0]._kind == "gru"
-    W, G = (GRUWeights, GRUGrads) if gru else (RNNWeights, RNNGrads)
+    W, G, ng = _STRUCTS[layers[0]._kind]
     w, g = (W * len(layers))(), (G * len(layers))() if outs is not None else None
     for d, layer in enumerate(layers):
         ps = layer._params()
-        if gru:
-            for k in range(3):
-                w[d].wx[k], w[d].wh[k], w[d].b[k] = (ps[k].data.data_ptr(), ps[3 + k].data.data_ptr(), ps[6 + k].data.data_ptr())
+        if ng > 1:                                          # wx[ng] | wh[ng] | b[ng], the order of _params()
+            for k in range(ng):
+                w[d].wx[k], w[d].wh[k], w[d].b[k] = (ps[k].data.data_ptr(), ps[ng + k].data.data_ptr(), ps[2 * ng + k].data.data_ptr())
                 if outs is not None:
-                    g[d].dwx[k], g[d].dwh[k], g[d].db[k] = (outs[d][k].data_ptr(), outs[d][3 + k].data_ptr(), outs[d][6 + k].data_ptr())
+                    g[d].dwx[k], g[d].dwh[k], g[d].db[k] = (outs[d][k].data_ptr(), outs[d][ng + k].data_ptr(), outs[d][2 * ng + k].data_ptr())
         else:
             w[d].wx, w[d].wh, w[d].b = (p.data.data_ptr() for p in ps)
             if outs is not None:
@@ -203,13 +62,13 @@ def _rec_structs(layers, outs=None):
     return w, g
 
 
-def _rec_forward(layers, X, h0, hT):
+def _rec_forward(layers, X, h0, hT, c0=None, cT=None):
     """One projection + ONE recurrence launch for the len(layers) directions.  h0: [ndir, B, H] or None; hT: [ndir, B, H], receives the
-    last state (it may be h0 itself).  Returns (x, Y [ndir, B, T, H], saved)."""
+    last state (it may be h0 itself); c0 / cT: the LSTM's cell state likewise.  Returns (x, Y [ndir, B, T, H], saved)."""
     import torch
     first = layers[0]
     x = X.data if X.data.is_contiguous() else X.data.contiguous()
-    if X.ndim == 2:                                         # gru.py:230-231 / rnn.py:130-131: a single sequence is batch 1
+    if X.ndim == 2:                                         # lstm.py:262-263 / gru.py:230-231 / rnn.py:130-131: a single sequence is batch 1
         x = x.reshape(1, *x.shape)
     B, T, n_in = x.shape
     H, ndir = first.hidden_size, len(layers)
@@ -218,10 +77,15 @@ def _rec_forward(layers, X, h0, hT):
     w, _ = _rec_structs(layers)
     nl = NONLINEARITIES[first.nonlinearity]
     saved = dict(X=x, Y=Y, hprev=hprev_s, B=B, T=T, H=H, nl=nl, layers=layers, **{"in": n_in})
-    if first._kind == "gru":
+    if first._kind != "rnn":
         rnl = NONLINEARITIES[first.recurrent_nonlinearity]
-        gates = torch.empty((ndir, B, T, 3 * _padded(H)), dtype=torch.float32, device="cuda")
+        gates = torch.empty((ndir, B, T, _STRUCTS[first._kind][2] * _padded(H)), dtype=torch.float32, device="cuda")
         saved.update(gates=gates, rnl=rnl)
+    if first._kind == "lstm":
+        cell = torch.empty((B, T + 1, H), dtype=torch.float32, device="cuda")
+        saved.update(cell=cell)
+        call_hip_function("nnhipLSTMForward", x, w, h0, c0, Y, gates, cell, hprev_s, hT, cT, B, T, n_in, H, nl, rnl, get_current_stream_ptr())
+    elif first._kind == "gru":
         call_hip_function("nnhipGRUForward", x, w, h0, Y, gates, hprev_s, hT, B, T, n_in, H, nl, rnl, ndir, get_current_stream_ptr())
     else:
         call_hip_function("nnhipRNNForward", x, w, h0, Y, hprev_s, hT, B, T, n_in, H, nl, ndir, get_current_stream_ptr())
@@ -236,7 +100,10 @@ def _rec_backward(saved, X, dY, dYlast):
     dX = X.xp.empty((B, T, n_in), dtype=np.float32) if X.requires_grad else None
     outs = [[_grad_out(p, p.data) for p in layer._params()] for layer in layers]
     w, g = _rec_structs(layers, outs)
-    if layers[0]._kind == "gru":
+    if layers[0]._kind == "lstm":
+        call_hip_function("nnhipLSTMBackward", s["X"], w, s["gates"], s["cell"], s["hprev"], dY, dYlast, dX, g, B, T, n_in, H, s["nl"], s["rnl"],
+                          get_current_stream_ptr())
+    elif layers[0]._kind == "gru":
         call_hip_function("nnhipGRUBackward", s["X"], w, s["gates"], s["hprev"], dY, dYlast, dX, g, B, T, n_in, H, s["nl"], s["rnl"], ndir,
                           get_current_stream_ptr())
     else:
@@ -250,7 +117,9 @@ def _rec_backward(saved, X, dY, dYlast):
 
 
 class _HIPRecurrentTensor(Tensor):
-    """One output of HIPGRU / HIPRNN: `which` is "all" or "last"; each output has its own BPTT grad_fn (gru.py:344-352, rnn.py:179-187)."""
+    """One output of HIPLSTM / HIPGRU / HIPRNN.  `which` is "all" (the gradient of every h_t) or "last" (the gradient of the last h
+    alone); each output has its own BPTT grad_fn, as in the reference (lstm.py:400-408, gru.py:344-352, rnn.py:179-187) -- with
+    return_sequences="both" the two passes add up in X and the parameters because the gradient is linear."""
 
     def __init__(self, data, args, device, saved, which):
         super().__init__(data, args, saved["layers"][0]._kind, device=device, _nocopy=True)
@@ -263,8 +132,9 @@ class _HIPRecurrentTensor(Tensor):
 
 
 class _HIPRecurrent(Module):
-    """What HIPGRU and HIPRNN share: the state handling and the single-direction call."""
+    """What HIPLSTM, HIPGRU and HIPRNN share: the input checks, the state handling and the single-direction call."""
     _kind = ""
+    _states = ("hprev",)                                    # the carried states, in the order _run takes them
 
     def _check(self, X):
         if not isinstance(X, Tensor):
@@ -279,34 +149,96 @@ class _HIPRecurrent(Module):
             raise ValueError("input_size must be equal to input shape[2]")
         return B
 
-    def _run(self, X, hprev):
+    def _sequences(self):
+        rs = self.return_sequences
+        return "all" if rs == "all" or rs is True else "last" if rs == "last" or rs is False else "both"
+
+    def _run(self, X, *given):
         import torch
         B, H = self._check(X), self.hidden_size
         if not self.cycled_states:
-            self.hprev = _array(hprev)
-        if self.hprev is not None and tuple(self.hprev.shape) != (B, H):
-            raise ValueError("hprev shape must be equal to (batch_size, 1, hidden_size)")
-        if self.cycled_states and self.hprev is None:
-            self.hprev = torch.zeros((B, H), dtype=torch.float32, device="cuda")
-        h0 = None if self.hprev is None else self.hprev.contiguous().to(torch.float32)
+            for name, v in zip(self._states, given):
+                setattr(self, name, _array(v))
+        for name in self._states:
+            state = getattr(self, name)
+            if state is not None and tuple(state.shape) != (B, H):
+                raise ValueError(f"{name} shape must be equal to (batch_size, 1, hidden_size)")
+            if self.cycled_states and state is None:
+                setattr(self, name, torch.zeros((B, H), dtype=torch.float32, device="cuda"))
+        states = [getattr(self, name) for name in self._states]
+        first = [None if s is None else s.contiguous().to(torch.float32) for s in states]
         last = torch.empty((B, 1, H), dtype=torch.float32, device="cuda")
-        # cycled: the kernel reads the state buffer and writes the new state into the same buffer (each element by its owner thread)
-        x, Y, saved = _rec_forward([self], X, h0, self.hprev if self.cycled_states else last)
+        # cycled: the kernel reads the state buffers and writes the new state into the same buffers (each element by its owner thread)
+        final = states if self.cycled_states else [last, None]
+        x, Y, saved = _rec_forward([self], X, *(s for pair in zip(first, final) for s in pair))     # h0, hT (, c0, cT)
         if self.cycled_states:
             last.copy_(self.hprev.reshape(B, 1, H))
         args = (X, *self._params())
-        T = x.shape[1]
-        rs = self.return_sequences
-        if rs == "all" or rs is True:
-            return _HIPRecurrentTensor(Y.reshape(B, T, H), args, self.device, saved, "all")
-        if rs == "last" or rs is False:
-            return _HIPRecurrentTensor(last, args, self.device, saved, "last")
-        return (_HIPRecurrentTensor(Y.reshape(B, T, H), args, self.device, saved, "all"),
-                _HIPRecurrentTensor(last, args, self.device, saved, "last"))
+        outs = {"all": Y.reshape(B, x.shape[1], H), "last": last}
+        which = self._sequences()
+        if which == "both":
+            return tuple(_HIPRecurrentTensor(outs[k], args, self.device, saved, k) for k in ("all", "last"))
+        return _HIPRecurrentTensor(outs[which], args, self.device, saved, which)
 
 
 def _uniform_param(stdv, shape):
     return Parameter(Tensor(np.random.uniform(-stdv, stdv, shape), dtype=np.float32))
+
+
+class HIPLSTM(_HIPRecurrent):
+    """neunet.nn.LSTM (lstm.py:168-252) on nnhipLSTMForward / nnhipLSTMBackward.  Differences from the reference, both deliberate:
+      * bias=False raises: the reference's `a + b + bias if bias is not None else +0` (lstm.py:313-319) parses as
+        `(a + b + bias) if ... else 0`, so without a bias every pre-activation is 0 and the layer outputs zeros whatever the input;
+      * with cycled_states the carried (h, c) live in module-owned device buffers that the kernel itself rewrites, so a replayed
+        hipGraph carries them from replay to replay exactly as eager calls do.  Their shape is (batch, hidden)."""
+    _kind = "lstm"
+    _states = ("hprev", "cprev")
+
+    def __init__(self, input_size: int, hidden_size: int, nonlinearity: str = "tanh", recurrent_nonlinearity: str = "sigmoid",
+                 return_sequences: Union[str, bool] = "both", bias: bool = True, cycled_states: bool = False, device="cuda"):
+        super().__init__()
+        for name in (nonlinearity, recurrent_nonlinearity):
+            if name not in NONLINEARITIES:
+                raise ValueError(f"unknown nonlinearity {name!r}: one of {sorted(NONLINEARITIES)} (lstm.py:460)")
+        if not bias:
+            raise ValueError("LSTM(bias=False) is not supported: in the reference it outputs zeros whatever the input "
+                             "(neunet/nn/layers/lstm.py:318 -- the conditional expression drops the whole pre-activation)")
+        if return_sequences not in _RS:                        # by ==, not _check_return_sequences' identity: 1 / 0 pass as True / False
+            raise ValueError(f"return_sequences must be 'both', 'all', 'last', True or False, got {return_sequences!r}")
+        self.input_size, self.hidden_size = input_size, hidden_size
+        self.nonlinearity, self.recurrent_nonlinearity = nonlinearity, recurrent_nonlinearity
+        self.return_sequences, self.cycled_states = return_sequences, cycled_states
+        stdv = 1.0 / np.sqrt(hidden_size)
+        # drawn from the global generator in the reference's order and dtype (float64 draws, stored as float32; lstm.py:187-242)
+        for gate in "fioc":
+            setattr(self, f"weight_{gate}", _uniform_param(stdv, (input_size, hidden_size)))
+        for gate in "fioc":
+            setattr(self, f"weight_h{gate}", _uniform_param(stdv, (hidden_size, hidden_size)))
+        for gate in "fioc":
+            setattr(self, f"bias_{gate}", Parameter(Tensor(np.zeros(hidden_size), dtype=np.float32)))
+        self.cprev = None
+        self.hprev = None
+        self.to(device)
+
+    def _params(self):
+        return [self.weight_f, self.weight_i, self.weight_o, self.weight_c, self.weight_hf, self.weight_hi, self.weight_ho,
+                self.weight_hc, self.bias_f, self.bias_i, self.bias_o, self.bias_c]
+
+    def _check(self, X):
+        B = super()._check(X)
+        if self.hidden_size > MAX_HIDDEN:                       # at the call, not at construction as for GRU / RNN
+            raise ValueError(f"hidden_size {self.hidden_size} > {MAX_HIDDEN} is not supported by the HIP recurrence kernels")
+        return B
+
+    def _sequences(self):
+        rs = self.return_sequences                              # by ==, as the constructor's check
+        return "all" if rs in ("all", True) else "last" if rs in ("last", False) else "both"
+
+    def forward(self, X: Tensor, hprev=None, cprev=None):
+        return self._run(X, hprev, cprev)
+
+    def __call__(self, X, hprev=None, cprev=None):
+        return self.forward(X, hprev, cprev)
 
 
 class HIPGRU(_HIPRecurrent):

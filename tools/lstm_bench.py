@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""nn.LSTM timings at the recurrent digits classifier's shape (B 100, T 28, H 128; examples/recurrent_classifier.py).
+"""nn.LSTM timings at the recurrent digits classifier's shape (B 100, T 28, H 128; examples/recurrent_classifier.py) and at H 256 / 512
+(two and four hidden tiles per wave: lstm_fwd_kernel<false, 2 / 4>, lstm_bwd_kernel<false, 2 / 4>).
 
-    python tools/lstm_bench.py [--reps 50]
+    python tools/lstm_bench.py [--reps 50] [--hidden 128 256 512]
 
-Per layer (in 28 and in 128): forward and backward entry points (projection GEMM + recurrence, recurrence + parameter GEMMs) from
+Per --hidden size and layer (in 28 and in H): forward and backward entry points (projection GEMM + recurrence, recurrence + parameter GEMMs) from
 HIP events, median of --reps, and the recurrence kernels alone per timestep (torch.profiler device times of lstm_fwd_kernel /
 lstm_bwd_kernel).  Then the graph-replayed classifier training step: ms per step, samples/s and kernel launches per step.
 Prints one JSON line."""
-import ctypes
 import json
 import os
 import statistics
@@ -52,21 +52,21 @@ def main():
     import torch
     import neunet_hip
     from neunet_hip import _lib
-    from neunet_hip.nn.experimental.recurrent import _padded, _weights_struct
+    from neunet_hip.nn.experimental.recurrent import _padded, _rec_structs
     import neunet_hip.nn as nn
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--hidden", type=int, nargs="+", default=[128, 256, 512])
     a = ap.parse_args()
     neunet_hip.load_library()
-    B, T, H = 100, 28, 128
+    B, T = 100, 28
     st = _lib.get_current_stream_ptr
-    res = {"B": B, "T": T, "H": H, "resident": os.environ.get("NNHIP_LSTM_RESIDENT", "1") != "0"}
+    res = {"B": B, "T": T, "resident": os.environ.get("NNHIP_LSTM_RESIDENT", "1") != "0"}
     np.random.seed(0)
-    for n_in in (28, 128):
+    for H, n_in in ((H, n_in) for H in a.hidden for n_in in (28, H)):
         m = nn.LSTM(n_in, H)
         ps = m.parameters()
-        w = _weights_struct(ps)
         Hp = _padded(H)
         X = torch.rand((B, T, n_in), device="cuda") * 2 - 1
         Y, hp = (torch.empty((B, T, H), device="cuda") for _ in range(2))
@@ -75,24 +75,20 @@ def main():
         dY = torch.rand((B, T, H), device="cuda")
         dX = torch.empty_like(X)
         grads = [torch.empty_like(p.data) for p in ps]
-        g = _lib.LSTMGrads()
-        for k in range(4):
-            g.dwx[k], g.dwh[k], g.db[k] = grads[k].data_ptr(), grads[4 + k].data_ptr(), grads[8 + k].data_ptr()
+        w, g = _rec_structs([m], [grads])
 
         def fwd():
-            _lib.call_hip_function("nnhipLSTMForward", X, ctypes.byref(w), None, None, Y, gates, cell, hp, None, None,
-                                   B, T, n_in, H, 0, 1, st())
+            _lib.call_hip_function("nnhipLSTMForward", X, w, None, None, Y, gates, cell, hp, None, None, B, T, n_in, H, 0, 1, st())
 
         def bwd():
-            _lib.call_hip_function("nnhipLSTMBackward", X, ctypes.byref(w), gates, cell, hp, dY, None, dX, ctypes.byref(g),
-                                   B, T, n_in, H, 0, 1, st())
+            _lib.call_hip_function("nnhipLSTMBackward", X, w, gates, cell, hp, dY, None, dX, g, B, T, n_in, H, 0, 1, st())
         for _ in range(5):
             fwd()
             bwd()
         torch.cuda.synchronize()
         kf = kernel_medians(fwd, a.reps, ["lstm_fwd_kernel"])["lstm_fwd_kernel"]
         kb = kernel_medians(bwd, a.reps, ["lstm_bwd_kernel"])["lstm_bwd_kernel"]
-        res[f"in{n_in}"] = {"fwd_us": round(event_median(fwd, a.reps), 1), "bwd_us": round(event_median(bwd, a.reps), 1),
+        res[f"h{H}_in{n_in}"] = {"fwd_us": round(event_median(fwd, a.reps), 1), "bwd_us": round(event_median(bwd, a.reps), 1),
                             "fwd_recurrence_us": kf and round(kf, 1), "bwd_recurrence_us": kb and round(kb, 1),
                             "fwd_us_per_step": kf and round(kf / T, 2), "bwd_us_per_step": kb and round(kb / T, 2)}
 
