@@ -235,6 +235,8 @@ int nnhipLinearReLULinearBackwardAdam(const float* X1, const float* H, const flo
  * default training step gets the backward + Adam launch without opting in).  No device work.  ABI 209 */
 int nnhipLinearReLULinearBackwardFits(int64_t rows, int64_t in1, int64_t hidden, int64_t out2, int32_t with_adam);
 /* O = act(X*W^T + b), activation in the GEMM epilogue: 1 = swish(beta) without saving z, 2 = relu, 3 = sigmoid.
+ * Activation 2 is np.maximum(0, z) (activations.py:55), as nnhipReLUForward: a NaN in z stays NaN, -0 becomes +0, on
+ * every kernel family the call can reach (small, 128x128 float4 / scalar epilogue, split-K reduce).
  * One launch for what `act(Linear(x))` is on the reference's tape (linear.py:48-58 + activations.py); the host side
  * uses it when an activation module is applied to a Linear output nobody else has looked at yet. */
 int nnhipLinearActivationForward(const float* X, const float* W, const float* b, float* O, int64_t rows,

@@ -452,7 +452,7 @@ __device__ __forceinline__ void splitk_reduce_body(const ReduceArgs& r, const in
             swish_fwd_d_(s, beta, s, d);
             if (preact) preact[m * ldc + n] = d;
         } else if (act == ACT_RELU) {
-            s = fmaxf(s, 0.f);
+            s = !(s <= 0.f) ? s : 0.f;       // np.maximum(0, z): NaN stays NaN (fmaxf would drop it)
         } else if (act == ACT_SIGMOID) {
             s = sigmoid_fast_(s);
         }

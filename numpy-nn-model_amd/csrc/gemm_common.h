@@ -260,7 +260,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[2][2], const GemmPar
                             swish_fwd_d_(v.z, p.beta, v.z, d.z); swish_fwd_d_(v.w, p.beta, v.w, d.w);
                             if (p.preact) *reinterpret_cast<float4*>(p.preact + c_off + row * ldc + col) = d;
                         } else if (p.act == ACT_RELU) {
-                            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                            // np.maximum(0, z): NaN stays NaN (fmaxf would return the other operand), -0 becomes +0 -- as nnhipReLUForward
+                            v.x = !(v.x <= 0.f) ? v.x : 0.f; v.y = !(v.y <= 0.f) ? v.y : 0.f;
+                            v.z = !(v.z <= 0.f) ? v.z : 0.f; v.w = !(v.w <= 0.f) ? v.w : 0.f;
                         } else if (p.act == ACT_SIGMOID) {
                             v.x = sigmoid_fast_(v.x); v.y = sigmoid_fast_(v.y); v.z = sigmoid_fast_(v.z); v.w = sigmoid_fast_(v.w);
                         }
@@ -303,7 +305,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[2][2], const GemmPar
                         swish_fwd_d_(v, p.beta, v, d);
                         if (p.preact) p.preact[c_off + row * ldc + col] = d;
                     } else if (p.act == ACT_RELU) {
-                        v = fmaxf(v, 0.f);
+                        v = !(v <= 0.f) ? v : 0.f;             // NaN stays NaN, as above
                     } else if (p.act == ACT_SIGMOID) {
                         v = sigmoid_fast_(v);
                     }

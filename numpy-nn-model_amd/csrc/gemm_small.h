@@ -153,7 +153,7 @@ __device__ __forceinline__ void sg_tile16(const SmallGemmParams& p, int bx, int 
                 swish_fwd_d_(v, p.beta, v, d);
                 if (p.preact) p.preact[row * p.ldc + col] = d;
             } else if (p.act == SG_ACT_RELU) {
-                v = fmaxf(v, 0.f);
+                v = !(v <= 0.f) ? v : 0.f;       // np.maximum(0, z): NaN stays NaN (fmaxf would drop it)
             } else if (p.act == SG_ACT_SIGMOID) {
                 v = sigmoid_fast_(v);
             }

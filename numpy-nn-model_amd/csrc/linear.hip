@@ -302,7 +302,7 @@ extern "C" int nnhipLinearModuleBackwardAct(const float* X, const float* W, cons
 }
 
 // O = act(X W^T + b) with the activation in the GEMM epilogue: activation 1 = swish(beta) (no pre-activation saved; use
-// nnhipLinearSwishForward to keep z), 2 = relu, 3 = sigmoid.  What `act(Linear(x))` computes on the reference's tape
+// nnhipLinearSwishForward to keep z), 2 = relu = np.maximum(0, z) (a NaN in z stays NaN, as nnhipReLUForward), 3 = sigmoid.  What `act(Linear(x))` computes on the reference's tape
 // (neunet/nn/layers/linear.py:48-58 followed by activations.py:54-56 / 221-233 / 20-25) in one launch.
 extern "C" int nnhipLinearActivationForward(const float* X, const float* W, const float* b, float* O, int64_t rows,
                                             int64_t in_features, int64_t out_features, int32_t activation, float beta,
