@@ -688,6 +688,72 @@ int nnhipGaussianReparamBackward(const float* dz, const float* eps, const float*
 int nnhipGaussianKLDForwardBackward(const float* mu, const float* logvar, float* loss, float* dmu, float* dlogvar, int64_t n,
                                     nnhipStream_t stream);
 
+/* ---- the remaining activations and losses of neunet.nn (ABI 222) ----------------------------------------------------------------
+ * Softplus, Softsign, Mish, TanhExp, ELU, SELU (neunet/nn/activations.py:140-194, 250-383) and Tensor.log (neunet/autograd.py:357)
+ * as functors on the elementwise map kernels.  out = f(in) ; dIn = dOut * f'(in): the backward reads the forward INPUT (12 B per
+ * element), never the output.  `alpha` is ELU's, ignored by every other kind.  size 0: nothing to do.
+ * The reference's float32 expressions overflow or cancel -- log(1 + exp(x)) is inf above 88 and exactly 0 below -17, the Mish
+ * backward forms exp(3x), the TanhExp backward inf * 0 above 88, the ELU backward's alpha + f cancels -- so the kernels evaluate the
+ * SAME mathematical functions in forms that stay finite and keep relative accuracy (as nnhipGELUForward does):
+ *   NNHIP_ACT_SOFTPLUS  max(x, 0) + log1p(exp(-|x|))                    f' = sigmoid(x)
+ *   NNHIP_ACT_SOFTSIGN  x / (1 + |x|)                                   f' = 1 / (1 + |x|)^2
+ *   NNHIP_ACT_MISH      x t, t = tanh(softplus(x)) = n (n + 2) / (n (n + 2) + 2), n = exp(x)
+ *                                                                       f' = t + x sigmoid(x) (1 - t^2)
+ *   NNHIP_ACT_TANHEXP   x t, t = tanh(exp(x))                           f' = t + x exp(x) (1 - t^2); the second term is exactly 0
+ *                                                                            once 1 - t^2 is 0: no inf * 0
+ *   NNHIP_ACT_ELU       x <= 0 ? alpha expm1(x) : x                     f' = x <= 0 ? alpha exp(x) : 1   (alpha at x = 0)
+ *   NNHIP_ACT_SELU      lambda (x > 0 ? x : a expm1(x))                 f' = lambda (x > 0 ? 1 : a exp(x)) (lambda a at x = 0);
+ *                       lambda, a: the reference's two constants (activations.py:372-373)
+ *   NNHIP_ACT_LOG       log(x), literally: log(0) = -inf, negative -> NaN  f' = 1 / x
+ * A NaN input gives a NaN output and a NaN gradient in every kind. */
+#define NNHIP_ACT_SOFTPLUS 0
+#define NNHIP_ACT_SOFTSIGN 1
+#define NNHIP_ACT_MISH 2
+#define NNHIP_ACT_TANHEXP 3
+#define NNHIP_ACT_ELU 4
+#define NNHIP_ACT_SELU 5
+#define NNHIP_ACT_LOG 6
+int nnhipActivationForward(int kind, float* out, const float* in, float alpha, int64_t size, nnhipStream_t stream);
+int nnhipActivationBackward(int kind, float* dIn, const float* dOut, const float* in, float alpha, int64_t size,
+                            nnhipStream_t stream);
+/* LogSoftmax (neunet/nn/activations.py:462-492) over slices addressed like nnhipSoftmaxForward's (num_slices, slice_size, stride),
+ * with the same three layouts and the same dispatch.  y = x - m - log(sum exp(x - m)), m the slice's maximum, the slice held in
+ * registers between the passes; dX = dY - exp(Y) * sum_c dY, Y the forward OUTPUT.  Sums in a fixed order, no atomics (reruns are
+ * bit-identical), no workspace.  A zero size is a no-op. */
+int nnhipLogSoftmaxForward(float* out, const float* in, int64_t num_slices, int64_t slice_size, int64_t stride,
+                           nnhipStream_t stream);
+int nnhipLogSoftmaxBackward(float* dX, const float* dY, const float* Y, int64_t num_slices, int64_t slice_size, int64_t stride,
+                            nnhipStream_t stream);
+/* NLLLoss (neunet/nn/losses.py:83-126).  logp [outer, n_cols, inner] (the reference's [N, C] is inner = 1, its [N, C, d1, ...] is
+ * inner = prod d), labels [outer, inner] of label_bytes = 2 / 4 / 8 (int16 / int32 / int64), class_weight [n_cols] or NULL (ones).
+ * Per position p = (n, i) with label y: term = -logp[n, y, i] * w[y] when y != ignore_index and 0 <= y < n_cols, else 0 -- an ignored
+ * or out-of-range position is never dereferenced, in logp or in the weights (the reference indexes weight[y] BEFORE it masks:
+ * its default ignore_index = -100 raises IndexError below 100 classes and reads class C - 100 above).  reduction 'n': loss[p] =
+ * term; 's': loss[0] = sum; 'm': loss[0] = sum / sum_p w[y] [p counts], the denominator derived inside the launch (no host read); a
+ * zero denominator gives loss 0 and a zero gradient (nnhipCrossEntropyLossEx's rule; the reference gives NaN).
+ * dlogp (may be NULL): the dense gradient [outer, n_cols, inner], zero-filled, plus one value per counted position, already scaled
+ * for 'm' / 's'.  pos_grad (may be NULL): that one value per position, [outer * inner] (0 where the position does not count) -- the
+ * sparse form nnhipLogSoftmaxNLLBackward consumes.  One block up to 16384 positions; beyond, per-block partial sums in the library
+ * workspace, a one-block finish and a gradient pass.  No float atomics: reruns are bit-identical. */
+int nnhipNLLLossForwardBackward(const float* logp, const void* labels, int32_t label_bytes, const float* class_weight_or_null,
+                                int64_t ignore_index, int64_t outer, int64_t n_cols, int64_t inner, char reduction, float* loss,
+                                float* dlogp_or_null, float* pos_grad_or_null, nnhipStream_t stream);
+/* NLLLoss(LogSoftmax(X)) for 2-D [n_rows, n_cols] over axis 1 (the reference's own CrossEntropyLoss, losses.py:66-77), backward in
+ * one pass: dX[n, c] = g_n ([c == y_n] - exp(Y[n, c])) u, Y the LogSoftmax output, g_n = pos_grad[n] (as written by
+ * nnhipNLLLossForwardBackward), u the scalar upstream gradient read from the device (NULL: 1).  Reads Y once and writes dX once:
+ * the dense [N, C] gradient of the NLL never exists.  Rows with g_n == 0 (ignored) are written as zeros. */
+int nnhipLogSoftmaxNLLBackward(float* dX, const float* Y, const void* labels, int32_t label_bytes, const float* pos_grad,
+                               const float* upstream_scalar_or_null, int64_t n_rows, int64_t n_cols, nnhipStream_t stream);
+/* L1Loss (neunet/nn/losses.py:129-146): term = |p - t|; dpred (may be NULL) = sign(p - t) * scale, sign(0) = 0 as np.sign
+ * (neunet/autograd.py:599).  reduction 'm' (scale 1/n), 's' (1) or 'n' (loss[0..n) = the terms, scale 1).  n > 0. */
+int nnhipL1LossForwardBackward(const float* pred, const float* target, float* loss, float* dpred, int64_t n, char reduction,
+                               nnhipStream_t stream);
+/* KLDivLoss (neunet/nn/losses.py:152-175): term = t (log t - p), or with log_target != 0 exp(t) (t - p) -- the reference's expression
+ * literally, so t = 0 gives NaN as np.log does.  dpred (may be NULL) = -t * scale or -exp(t) * scale.  reduction 'm' (scale 1/n),
+ * 'b' (batchmean: 1/batch, batch > 0), 's' (1) or 'n' (the terms).  The target receives no gradient.  n > 0. */
+int nnhipKLDivLossForwardBackward(const float* pred, const float* target, float* loss, float* dpred, int64_t n, int64_t batch,
+                                  int log_target, char reduction, nnhipStream_t stream);
+
 /* ---- vector quantisation (examples/vqvae.ipynb).  ABI 219 --------------------------------------------------------------------
  * nnhipVQNearest replaces VQVAE.quantize: `similarity = matmul(z, codebook.weight.T)`, `distances = sum(z**2, axis=1, keepdims=True)
  * + sum(codebook.weight**2, axis=1) - 2 * similarity`, `min_indices = argmin(distances, axis=1)`, `z_q = codebook(min_indices)`.

@@ -147,6 +147,84 @@ struct GeluB {
 struct TanhF { __device__ float operator()(float x) const { return tanhf(x); } };
 // dIn = dOut * (1 - f^2), f the activation's OUTPUT   (neunet/nn/activations.py:107-110)
 struct TanhB { __device__ float operator()(float dy, float f) const { return dy * (1.0f - f * f); } };
+// ---- Softplus, Softsign, Mish, TanhExp, ELU, SELU, log (neunet/nn/activations.py:140-194, 250-383; neunet/autograd.py:357) ---------
+// The same mathematical functions as the reference's expressions, in forms that stay finite and keep relative accuracy where its
+// float32 ones overflow or cancel (include/neunet_hip.h lists them).  Every backward functor reads the forward INPUT.  A NaN input
+// gives NaN from every functor: no fmaxf / fminf on the value path (they drop a NaN), and the selects send a NaN down the branch
+// that computes with it.
+// log(1 + e) for 0 <= e <= 1: log(u) + (e - (u - 1)) / u with u = fl(1 + e) -- the second term puts back what the rounding of 1 + e
+// lost (exactly e once u == 1), so the result keeps its relative accuracy down to e = exp(-103)
+__device__ __forceinline__ float log1p_unit_(float e) {
+    const float u = 1.0f + e;
+    return fmaf(e - (u - 1.0f), __builtin_amdgcn_rcpf(u), logf(u));
+}
+// f = log(1 + exp(x)) = max(x, 0) + log1p(exp(-|x|))   (activations.py:156; |NaN| carries the NaN through the second term)
+struct SoftplusF {
+    __device__ float operator()(float x) const { return (x > 0.f ? x : 0.f) + log1p_unit_(exp_fast_(-fabsf(x))); }
+};
+// dx = dy * sigmoid(x)                                 (activations.py:146)
+struct SoftplusB { __device__ float operator()(float dy, float x) const { return dy * sigmoid_fast_(x); } };
+// f = x / (1 + |x|) ; dx = dy / (1 + |x|)^2            (activations.py:190, 180).  IEEE divisions: 1 + |x| reaches 3.4e38, whose
+// hardware reciprocal is a denormal
+struct SoftsignF { __device__ float operator()(float x) const { return x / (1.0f + fabsf(x)); } };
+struct SoftsignB {
+    __device__ float operator()(float dy, float x) const {
+        const float r = 1.0f / (1.0f + fabsf(x));
+        return dy * (r * r);
+    }
+};
+// Mish: f = x t, t = tanh(softplus(x)) (activations.py:274).  With n = exp(x): tanh(log(1 + n)) = ((1 + n)^2 - 1) / ((1 + n)^2 + 1) =
+// p / (p + 2), p = n (n + 2) -- one exp and one reciprocal, no log, no cancellation on either side (t -> n for x -> -inf).  Beyond
+// x = 20, p > 2e17 and t is 1 to the last bit (and n^2 would overflow at 44): f = x, f' = 1 there.
+// f' = t + x sigmoid(x) (1 - t^2), 1 - t^2 = (1 - t)(1 + t) = 2 (1 + t) / (p + 2), sigmoid(x) = n / (1 + n): the reference's
+// backward (activations.py:258-262) is the same derivative written with exp(3x), which overflows at x = 29.6.
+struct MishF {
+    __device__ float operator()(float x) const {
+        if (x > 20.f) return x;
+        const float n = exp_fast_(x), p = n * (n + 2.0f);
+        return x * (p * __builtin_amdgcn_rcpf(p + 2.0f));
+    }
+};
+struct MishB {
+    __device__ float operator()(float dy, float x) const {
+        if (x > 20.f) return dy;
+        const float n = exp_fast_(x), p = n * (n + 2.0f);
+        const float rq = __builtin_amdgcn_rcpf(p + 2.0f), t = p * rq;
+        const float sg = n * __builtin_amdgcn_rcpf(1.0f + n);
+        return dy * fmaf(x * sg, 2.0f * rq * (1.0f + t), t);
+    }
+};
+// TanhExp: f = x t, t = tanh(exp(x)) (activations.py:312); f' = t + x exp(x) (1 - t^2) (activations.py:301), with
+// 1 - t^2 = 4 q / (1 + q)^2, q = exp(-2 exp(x)) (no cancellation).  Above x = 88.7 exp(x) is inf and 1 - t^2 is 0: the second term
+// is exactly 0 from the moment 1 - t^2 is (x > ~3.9), so it is skipped there instead of forming inf * 0.
+struct TanhExpF { __device__ float operator()(float x) const { return x * tanhf(exp_fast_(x)); } };
+struct TanhExpB {
+    __device__ float operator()(float dy, float x) const {
+        const float n = exp_fast_(x), t = tanhf(n);
+        const float q = exp_fast_(-2.0f * n), r = __builtin_amdgcn_rcpf(1.0f + q);
+        const float omt2 = 4.0f * q * r * r;
+        return dy * (omt2 == 0.f ? t : fmaf(x * n, omt2, t));
+    }
+};
+// ELU: f = x <= 0 ? alpha (exp(x) - 1) : x (activations.py:349), expm1 instead of the cancelling exp(x) - 1;
+// f' = x <= 0 ? alpha exp(x) : 1 (activations.py:337 forms it as alpha + f, which cancels for alpha != 1).  f'(0) = alpha.
+struct EluF {
+    float alpha;
+    __device__ float operator()(float x) const { return x <= 0.f ? alpha * expm1f(x) : x; }
+};
+struct EluB {
+    float alpha;
+    __device__ float operator()(float dy, float x) const { return x > 0.f ? dy : dy * (alpha * exp_fast_(x)); }
+};
+// SELU: f = lambda (x > 0 ? x : a (exp(x) - 1)) ; f' = lambda (x > 0 ? 1 : a exp(x))   (activations.py:372-378, 363); f'(0) = lambda a
+constexpr float kSeluAlpha = 1.6732632423543772848170429916717f, kSeluLambda = 1.0507009873554804934193349852946f;
+struct SeluF { __device__ float operator()(float x) const { return kSeluLambda * (x > 0.f ? x : kSeluAlpha * expm1f(x)); } };
+struct SeluB {
+    __device__ float operator()(float dy, float x) const { return dy * (kSeluLambda * (x > 0.f ? 1.0f : kSeluAlpha * exp_fast_(x))); }
+};
+// Tensor.log (neunet/autograd.py:357): f = log(x), literally (log(0) = -inf, a negative x gives NaN) ; dx = dy / x
+struct LogF { __device__ float operator()(float x) const { return logf(x); } };
+struct LogB { __device__ float operator()(float dy, float x) const { return dy / x; } };
 struct ScaleF {
     float alpha;
     __device__ float operator()(float x) const { return alpha * x; }
@@ -324,6 +402,39 @@ extern "C" int nnhipTanhBackward(float* dIn, const float* dOut, const float* out
     if (size == 0) return 0;
     NNHIP_PTRS("nnhipTanhBackward", dIn, dOut, out);
     return launch_map2(dIn, dOut, out, size, TanhB{}, (hipStream_t)s, "tanh_backward");
+}
+extern "C" int nnhipActivationForward(int kind, float* out, const float* in, float alpha, int64_t size, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(kind >= NNHIP_ACT_SOFTPLUS && kind <= NNHIP_ACT_LOG, NNHIP_EINVAL, "nnhipActivationForward: unknown kind %d", kind);
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipActivationForward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipActivationForward", out, in);
+    hipStream_t st = (hipStream_t)s;
+    switch (kind) {
+        case NNHIP_ACT_SOFTPLUS: return launch_map1(out, in, size, SoftplusF{}, st, "softplus_forward");
+        case NNHIP_ACT_SOFTSIGN: return launch_map1(out, in, size, SoftsignF{}, st, "softsign_forward");
+        case NNHIP_ACT_MISH: return launch_map1(out, in, size, MishF{}, st, "mish_forward");
+        case NNHIP_ACT_TANHEXP: return launch_map1(out, in, size, TanhExpF{}, st, "tanhexp_forward");
+        case NNHIP_ACT_ELU: return launch_map1(out, in, size, EluF{alpha}, st, "elu_forward");
+        case NNHIP_ACT_SELU: return launch_map1(out, in, size, SeluF{}, st, "selu_forward");
+        default: return launch_map1(out, in, size, LogF{}, st, "log_forward");
+    }
+}
+extern "C" int nnhipActivationBackward(int kind, float* dIn, const float* dOut, const float* in, float alpha, int64_t size,
+                                       nnhipStream_t s) {
+    NNHIP_CHECK_ARG(kind >= NNHIP_ACT_SOFTPLUS && kind <= NNHIP_ACT_LOG, NNHIP_EINVAL, "nnhipActivationBackward: unknown kind %d", kind);
+    NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipActivationBackward: negative size");
+    if (size == 0) return 0;
+    NNHIP_PTRS("nnhipActivationBackward", dIn, dOut, in);
+    hipStream_t st = (hipStream_t)s;
+    switch (kind) {
+        case NNHIP_ACT_SOFTPLUS: return launch_map2(dIn, dOut, in, size, SoftplusB{}, st, "softplus_backward");
+        case NNHIP_ACT_SOFTSIGN: return launch_map2(dIn, dOut, in, size, SoftsignB{}, st, "softsign_backward");
+        case NNHIP_ACT_MISH: return launch_map2(dIn, dOut, in, size, MishB{}, st, "mish_backward");
+        case NNHIP_ACT_TANHEXP: return launch_map2(dIn, dOut, in, size, TanhExpB{}, st, "tanhexp_backward");
+        case NNHIP_ACT_ELU: return launch_map2(dIn, dOut, in, size, EluB{alpha}, st, "elu_backward");
+        case NNHIP_ACT_SELU: return launch_map2(dIn, dOut, in, size, SeluB{}, st, "selu_backward");
+        default: return launch_map2(dIn, dOut, in, size, LogB{}, st, "log_backward");
+    }
 }
 extern "C" int nnhipFusedSwishAndMul(float* out, const float* in, float beta, int64_t hidden,
                                      int64_t size, nnhipStream_t s) {

@@ -1677,6 +1677,131 @@ __global__ __launch_bounds__(1024) void softmax_masked_bwd_looped(float* dx, con
     }
 }
 
+// =================================================================================================
+// LogSoftmax   (neunet/nn/activations.py:476-489 fwd, 466-471 bwd), the layouts of Softmax above
+// =================================================================================================
+// y = x - m - log(sum exp(x - m)): the row stays in registers between the passes.  The sum is >= 1 (the maximum's own term), so the
+// log is taken of a number in [1, cols].  A -inf entry among finite ones gives -inf there and finite values elsewhere.
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_fwd_rows(
+    float* __restrict__ out, const float* __restrict__ in, int64_t rows, int64_t cols, int nt) {
+    ROW_PROLOGUE(TPR)
+    RowTile<TPR, NV, VEC> r;
+    r.load(in + row * cols, cols, t, -INFINITY, nt);
+    float m = r.x[0];
+#pragma unroll
+    for (int e = 1; e < r.NE; ++e) m = fmaxf(m, r.x[e]);
+    m = row_max<TPR>(m, red);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) {
+        r.x[e] -= m;
+        s += exp_fast_(r.x[e]);  // exp(-inf) = 0 for the padding lanes
+    }
+    s = row_sum<TPR>(s, red);
+    const float lse = logf(s);
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) r.x[e] -= lse;
+    r.store(out + row * cols, cols, t);
+}
+// dx = dy - exp(y) * sum_c dy
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_bwd_rows(
+    float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y, int64_t rows,
+    int64_t cols, int nt) {
+    ROW_PROLOGUE(TPR)
+    RowTile<TPR, NV, VEC> g, f;
+    g.load(dy + row * cols, cols, t, 0.f, nt);
+    f.load(y + row * cols, cols, t, 0.f, nt);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < g.NE; ++e) s += g.x[e];
+    s = row_sum<TPR>(s, red);
+#pragma unroll
+    for (int e = 0; e < g.NE; ++e) g.x[e] = fmaf(-exp_fast_(f.x[e]), s, g.x[e]);
+    g.store(dx + row * cols, cols, t);
+}
+__global__ __launch_bounds__(256) void logsoftmax_fwd_strided(float* __restrict__ out, const float* __restrict__ in,
+                                                              int64_t num_slices, int64_t n, int64_t stride) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= num_slices) return;
+    const int64_t base = (s / stride) * n * stride + (s % stride);
+    float m = -INFINITY;
+    for (int64_t i = 0; i < n; ++i) m = fmaxf(m, in[base + i * stride]);
+    float d = 0.f;
+    for (int64_t i = 0; i < n; ++i) d += exp_fast_(in[base + i * stride] - m);
+    const float lse = logf(d);
+    for (int64_t i = 0; i < n; ++i) out[base + i * stride] = in[base + i * stride] - m - lse;
+}
+__global__ __launch_bounds__(256) void logsoftmax_bwd_strided(float* __restrict__ dx, const float* __restrict__ dy,
+                                                              const float* __restrict__ y, int64_t num_slices, int64_t n,
+                                                              int64_t stride) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= num_slices) return;
+    const int64_t base = (s / stride) * n * stride + (s % stride);
+    float d = 0.f;
+    for (int64_t i = 0; i < n; ++i) d += dy[base + i * stride];
+    for (int64_t i = 0; i < n; ++i) dx[base + i * stride] = fmaf(-exp_fast_(y[base + i * stride]), d, dy[base + i * stride]);
+}
+__global__ __launch_bounds__(256) void logsoftmax_fwd_looped(float* __restrict__ out, const float* __restrict__ in, int64_t n) {
+    __shared__ float red[4];
+    const float* x = in + (int64_t)blockIdx.x * n;
+    float* o = out + (int64_t)blockIdx.x * n;
+    float m = -INFINITY;
+    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
+    m = block_max<4>(m, red);
+    float d = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) d += exp_fast_(x[i] - m);
+    d = block_sum<4>(d, red);
+    const float lse = logf(d);
+    for (int64_t i = threadIdx.x; i < n; i += 256) o[i] = x[i] - m - lse;
+}
+__global__ __launch_bounds__(256) void logsoftmax_bwd_looped(float* __restrict__ dx, const float* __restrict__ dy,
+                                                             const float* __restrict__ y, int64_t n) {
+    __shared__ float red[4];
+    const int64_t b = (int64_t)blockIdx.x * n;
+    float d = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) d += dy[b + i];
+    d = block_sum<4>(d, red);
+    for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = fmaf(-exp_fast_(y[b + i]), d, dy[b + i]);
+}
+// NLLLoss(LogSoftmax(x)) backward in one pass: dx[n, c] = g_n ([c == y_n] - exp(Y[n, c])) u.  g_n = pos_grad[n] is the one value per
+// row the NLL entry wrote (0: the row is ignored, or its label is out of range -- zeros, and the label is not looked at), u the scalar
+// upstream gradient (a device word another kernel wrote: an agent-scope load).
+template <int TPR, int NV, bool VEC>
+__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_nll_bwd_rows(
+    float* __restrict__ dx, const float* __restrict__ y, const void* __restrict__ labels, int lbytes, const float* __restrict__ pos_grad,
+    const float* upstream, int64_t rows, int64_t cols, int nt) {
+    ROW_PROLOGUE(TPR)
+    RowTile<TPR, NV, VEC> f;
+    if (row >= rows) return;                  // (the kernel has no barrier: any thread may leave)
+    const float g0 = pos_grad[row];
+    if (g0 == 0.f) {
+#pragma unroll
+        for (int e = 0; e < f.NE; ++e) f.x[e] = 0.f;
+    } else {
+        const float g = g0 * (upstream ? ld_dev_f32(upstream) : 1.0f);
+        f.load(y + row * cols, cols, t, 0.f, nt);
+        const int64_t label = load_label(labels, row, lbytes);
+#pragma unroll
+        for (int e = 0; e < f.NE; ++e) f.x[e] = g * ((f.col(t, e) == label ? 1.0f : 0.f) - exp_fast_(f.x[e]));
+    }
+    f.store(dx + row * cols, cols, t);
+}
+__global__ __launch_bounds__(256) void logsoftmax_nll_bwd_looped(float* __restrict__ dx, const float* __restrict__ y,
+                                                                 const void* __restrict__ labels, int lbytes,
+                                                                 const float* __restrict__ pos_grad, const float* upstream, int64_t n) {
+    const int64_t row = blockIdx.x, b = row * n;
+    const float g0 = pos_grad[row];
+    if (g0 == 0.f) {
+        for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = 0.f;
+        return;
+    }
+    const float g = g0 * (upstream ? ld_dev_f32(upstream) : 1.0f);
+    const int64_t label = load_label(labels, row, lbytes);
+    for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = g * ((i == label ? 1.0f : 0.f) - exp_fast_(y[b + i]));
+}
+
 // Streaming loads for a [rows, cols] operand with row pitch ld?  Only when the tensor cannot be cache-resident anyway
 // (>= 128 MB: the producer's output is long gone from the 32 MB of L2 and mostly from the 256 MB MALL) and its rows are
 // whole 128-B lines (see RowTile::load).  NNHIP_ROW_NT=0/1 forces it off/on (developer switch).
@@ -1881,6 +2006,73 @@ extern "C" int nnhipSoftmaxBackward(float* dX, const float* dY, const float* Y, 
         });
     }
     NNHIP_LAUNCH_CHECK("softmax_backward");
+    return 0;
+}
+
+// ---- LogSoftmax -----------------------------------------------------------------------------------
+extern "C" int nnhipLogSoftmaxForward(float* out, const float* in, int64_t num_slices, int64_t slice_size, int64_t stride,
+                                      nnhipStream_t s) {
+    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipLogSoftmaxForward: negative size");
+    if (num_slices == 0 || slice_size == 0) return 0;
+    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipLogSoftmaxForward: stride must be >= 1");
+    NNHIP_CHECK_ARG(out && in, NNHIP_EINVAL, "nnhipLogSoftmaxForward: null pointer");
+    hipStream_t st = (hipStream_t)s;
+    if (stride != 1) {
+        hipLaunchKernelGGL(logsoftmax_fwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
+                           out, in, num_slices, slice_size, stride);
+    } else if (slice_size > kMaxRegRow) {
+        hipLaunchKernelGGL(logsoftmax_fwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, out, in, slice_size);
+    } else {
+        const bool vec = aligned16(out) && aligned16(in) && slice_size % 4 == 0;
+        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(logsoftmax_fwd_rows<tpr, nv, v>, num_slices, st, out, in, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        });
+    }
+    NNHIP_LAUNCH_CHECK("logsoftmax_forward");
+    return 0;
+}
+
+extern "C" int nnhipLogSoftmaxBackward(float* dX, const float* dY, const float* Y, int64_t num_slices, int64_t slice_size,
+                                       int64_t stride, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: negative size");
+    if (num_slices == 0 || slice_size == 0) return 0;
+    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: stride must be >= 1");
+    NNHIP_CHECK_ARG(dX && dY && Y, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: null pointer");
+    hipStream_t st = (hipStream_t)s;
+    if (stride != 1) {
+        hipLaunchKernelGGL(logsoftmax_bwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
+                           dX, dY, Y, num_slices, slice_size, stride);
+    } else if (slice_size > kMaxRegRow) {
+        hipLaunchKernelGGL(logsoftmax_bwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, dX, dY, Y, slice_size);
+    } else {
+        const bool vec = aligned16(dX) && aligned16(dY) && aligned16(Y) && slice_size % 4 == 0;
+        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(logsoftmax_bwd_rows<tpr, nv, v>, num_slices, st, dX, dY, Y, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
+        });
+    }
+    NNHIP_LAUNCH_CHECK("logsoftmax_backward");
+    return 0;
+}
+
+extern "C" int nnhipLogSoftmaxNLLBackward(float* dX, const float* Y, const void* labels, int32_t label_bytes, const float* pos_grad,
+                                          const float* upstream_scalar_or_null, int64_t n_rows, int64_t n_cols, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(n_rows >= 0 && n_cols >= 0, NNHIP_EINVAL, "nnhipLogSoftmaxNLLBackward: negative size");
+    NNHIP_CHECK_ARG(label_bytes == 2 || label_bytes == 4 || label_bytes == 8, NNHIP_EINVAL,
+                    "nnhipLogSoftmaxNLLBackward: label_bytes must be 2, 4 or 8");
+    if (n_rows == 0 || n_cols == 0) return 0;
+    NNHIP_CHECK_ARG(dX && Y && labels && pos_grad, NNHIP_EINVAL, "nnhipLogSoftmaxNLLBackward: null pointer");
+    hipStream_t st = (hipStream_t)s;
+    if (n_cols > kMaxRegRow) {
+        hipLaunchKernelGGL(logsoftmax_nll_bwd_looped, dim3((unsigned)n_rows), dim3(256), 0, st, dX, Y, labels, (int)label_bytes, pos_grad,
+                           upstream_scalar_or_null, n_cols);
+    } else {
+        const bool vec = aligned16(dX) && aligned16(Y) && n_cols % 4 == 0;
+        row_tier(n_cols, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(logsoftmax_nll_bwd_rows<tpr, nv, v>, n_rows, st, dX, Y, labels, (int)label_bytes, pos_grad, upstream_scalar_or_null,
+                            n_rows, n_cols, row_streaming(n_rows, n_cols, n_cols));
+        });
+    }
+    NNHIP_LAUNCH_CHECK("logsoftmax_nll_backward");
     return 0;
 }
 

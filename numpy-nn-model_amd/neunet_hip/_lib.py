@@ -231,6 +231,14 @@ _SIGNATURES = {
     "nnhipGaussianReparamForward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
     "nnhipGaussianReparamBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
     "nnhipGaussianKLDForwardBackward": (ctypes.c_int, [P, P, P, P, P, c_int64, c_void_p]),
+    "nnhipActivationForward": (ctypes.c_int, [ctypes.c_int, P, P, c_float, c_int64, c_void_p]),
+    "nnhipActivationBackward": (ctypes.c_int, [ctypes.c_int, P, P, P, c_float, c_int64, c_void_p]),
+    "nnhipLogSoftmaxForward": (ctypes.c_int, [P, P, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipLogSoftmaxBackward": (ctypes.c_int, [P, P, P, c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipNLLLossForwardBackward": (ctypes.c_int, [P, P, c_int32, P, c_int64, c_int64, c_int64, c_int64, c_char, P, P, P, c_void_p]),
+    "nnhipLogSoftmaxNLLBackward": (ctypes.c_int, [P, P, P, c_int32, P, P, c_int64, c_int64, c_void_p]),
+    "nnhipL1LossForwardBackward": (ctypes.c_int, [P, P, P, P, c_int64, c_char, c_void_p]),
+    "nnhipKLDivLossForwardBackward": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_int, c_char, c_void_p]),
     "nnhipVQNearest": (ctypes.c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipVQLossForwardBackward": (ctypes.c_int, [P, P, c_float, P, P, P, c_int64, c_void_p]),
     "nnhipScale": (ctypes.c_int, [P, c_float, c_int64, c_void_p]),

@@ -6,7 +6,7 @@ Restates the contract of neunet/autograd.py that the accelerated layers rely on 
   * backward: seed ones, DFS topological sort over `args`, replay `grad_fn(*args, grad=v.grad)`
     in reverse                                                        (autograd.py:965-1002)
 The ~45 elementwise/reduction ops of the reference Tensor are host NumPy glue and out of scope
-(SURVEY 2 #1); a few shape ops the hot-path callers need (reshape, scalar mul, add) are provided.
+(SURVEY 2 #1); the few ops the hot-path callers need (reshape, add, log) are provided.
 
 Device arrays: on device "cuda" `Tensor.data` is a torch.Tensor living in HBM (torch-ROCm plays the
 role CuPy plays in the reference: allocation + streams only); on "cpu" it is a numpy.ndarray and the
@@ -347,6 +347,12 @@ class Tensor:
         return out
 
     __add__ = add
+
+    def log(self) -> "Tensor":
+        """Natural logarithm on the tape (neunet/autograd.py:357): out = log(self), literally (log(0) = -inf, a negative entry gives
+        NaN); the backward is grad / self.  Device float32 only: one nnhipActivationForward launch (kind NNHIP_ACT_LOG)."""
+        from .nn.experimental.activations import ACT_LOG, hip_activation
+        return hip_activation(self, ACT_LOG, "log")
 
     def __repr__(self):
         return f"Tensor(shape={self.shape}, dtype={self.dtype}, device={self.device}, op={self.op})"

@@ -12,7 +12,10 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPSigmoid as Sigmoid, HIPLSTM as LSTM, HIPLayerNorm as LayerNorm, HIPGELU as GELU,
                            HIPCausalSelfAttention as CausalSelfAttention, KVCache, CrossAttentionMemory,
                            HIPConvTranspose2d as ConvTranspose2d, HIPBatchNorm1d as BatchNorm1d, HIPTanh as Tanh,
-                           HIPBCELoss as BCELoss, HIPGRU as GRU, HIPRNN as RNN, HIPBidirectional as Bidirectional)
+                           HIPBCELoss as BCELoss, HIPGRU as GRU, HIPRNN as RNN, HIPBidirectional as Bidirectional,
+                           HIPSoftplus as Softplus, HIPSoftsign as Softsign, HIPMish as Mish, HIPTanhExp as TanhExp,
+                           HIPELU as ELU, HIPSELU as SELU, HIPLogSoftmax as LogSoftmax, HIPNLLLoss as NLLLoss,
+                           HIPL1Loss as L1Loss, HIPKLDivLoss as KLDivLoss)
 
 
 class CrossEntropyLoss(HIPCrossEntropyLoss):

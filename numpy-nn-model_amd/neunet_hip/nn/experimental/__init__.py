@@ -1,10 +1,11 @@
 """HIP-accelerated layers: one-to-one counterparts of neunet/nn/experimental/*
 (the reference's CUDA* classes are also exported as aliases of the HIP* ones)."""
 from .activations import (CUDAFusedSwishAndMul, CUDASoftmax, CUDASwish, HIPFusedSwishAndMul, HIPGELU, HIPReLU,  # noqa: F401
-                          HIPSoftmax, HIPSwish, HIPTanh)
+                          HIPSoftmax, HIPSwish, HIPTanh, HIPSoftplus, HIPSoftsign, HIPMish, HIPTanhExp, HIPELU, HIPSELU,
+                          HIPLogSoftmax)
 from .linear import CUDALinear, HIPLinear  # noqa: F401
 from .linear_swish import CUDALinearSwish, HIPLinearSwish  # noqa: F401
-from .losses import CUDACrossEntropyLoss, HIPBCELoss, HIPCrossEntropyLoss  # noqa: F401
+from .losses import CUDACrossEntropyLoss, HIPBCELoss, HIPCrossEntropyLoss, HIPKLDivLoss, HIPL1Loss, HIPNLLLoss  # noqa: F401
 from .rmsnorm import CUDARMSNorm, HIPRMSNorm  # noqa: F401
 from .conv2d import HIPConv2d  # noqa: F401
 from .conv_transpose2d import HIPConvTranspose2d  # noqa: F401

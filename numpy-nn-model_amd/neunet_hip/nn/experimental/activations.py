@@ -1,6 +1,7 @@
 """HIP activations: drop-ins for CUDASwish (experimental/activations/swish/swish.py:92-120),
 CUDAFusedSwishAndMul (.../fused_swish_and_mul/fused_swish_and_mul.py:154-179), CUDASoftmax
-(.../softmax/softmax.py:139-169), plus HIPReLU (CPU reference: neunet/nn/activations.py:40-59) and HIPTanh (:107-126)."""
+(.../softmax/softmax.py:139-169), plus HIPReLU (CPU reference: neunet/nn/activations.py:40-59), HIPTanh (:107-126), HIPSoftplus,
+HIPSoftsign, HIPMish, HIPTanhExp, HIPELU, HIPSELU (:140-383) and HIPLogSoftmax (:462-492)."""
 import weakref
 
 import numpy as np
@@ -303,6 +304,152 @@ class HIPSoftmax(Module):
         f_x = x.xp.empty_like(x.data)
         hip_softmax_forward(x.data, f_x, self.axis)
         return _HIPSoftmaxTensor(f_x, [x, f_x, self.axis], "softmax", device=x.device)
+
+
+# ------------------------------------------------------------------------------------- LogSoftmax
+def hip_logsoftmax_forward(x, o, dim: int):
+    """neunet/nn/activations.py:485-488 -> nnhipLogSoftmaxForward: arbitrary axis through (num_slices, slice_size, stride)."""
+    _check_arrays(x, o)
+    if x.shape != o.shape:
+        raise ValueError("Input and output shapes must match")
+    x = contiguous(x)
+    n, s, st = _slices(x, dim)
+    call_hip_function("nnhipLogSoftmaxForward", o, x, n, s, st, get_current_stream_ptr())
+    return o
+
+
+def hip_logsoftmax_backward(grad_x, grad, f_x, dim: int):
+    """neunet/nn/activations.py:466-471: grad - exp(f_x) * grad.sum(axis) -> nnhipLogSoftmaxBackward."""
+    _check_arrays(grad_x, grad, f_x)
+    if grad_x.shape != grad.shape or grad_x.shape != f_x.shape:
+        raise ValueError("Input, output gradients and log-softmax shapes must match")
+    grad, f_x = contiguous(grad), contiguous(f_x)
+    n, s, st = _slices(f_x, dim)
+    call_hip_function("nnhipLogSoftmaxBackward", grad_x, grad, f_x, n, s, st, get_current_stream_ptr())
+    return grad_x
+
+
+class _HIPLogSoftmaxTensor(Tensor):
+    """args = [input, output, axis]: HIPNLLLoss looks at them to fold its backward into this node's (losses.py)."""
+
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+
+        def grad_fn(t: Tensor, f_x, axis, grad):
+            grad_x = t.xp.empty_like(f_x)
+            hip_logsoftmax_backward(grad_x, grad, f_x, axis)
+            t.apply_grad(grad_x)
+
+        self.grad_fn = grad_fn
+
+
+class HIPLogSoftmax(Module):
+    """neunet/nn/activations.py:476-492: x - max - log(sum(exp(x - max))) along `axis`; the tensor saves its output."""
+
+    def __init__(self, axis: int = 1):
+        super().__init__()
+        self.axis = axis
+
+    def forward(self, x: Tensor):
+        require_device_f32(x)
+        f_x = x.xp.empty_like(x.data)
+        hip_logsoftmax_forward(x.data, f_x, self.axis)
+        return _HIPLogSoftmaxTensor(f_x, [x, f_x, self.axis], "log_softmax", device=x.device)
+
+
+# ---------------------------------------------- Softplus, Softsign, Mish, TanhExp, ELU, SELU, log
+ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_MISH, ACT_TANHEXP, ACT_ELU, ACT_SELU, ACT_LOG = range(7)     # NNHIP_ACT_* (include/neunet_hip.h)
+
+
+class _HIPActivationTensor(Tensor):
+    """args = [input, kind, alpha]: the backward reads the saved INPUT (nnhipActivationBackward)."""
+
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+
+        def grad_fn(t: Tensor, kind, alpha, grad):
+            xd = contiguous(t.data)
+            grad_input = t.xp.empty_like(xd)
+            call_hip_function("nnhipActivationBackward", kind, grad_input, contiguous(grad), xd, float(alpha), xd.numel(),
+                              get_current_stream_ptr())
+            t.apply_grad(grad_input)
+
+        self.grad_fn = grad_fn
+
+
+def hip_activation(x: Tensor, kind: int, op: str, alpha: float = 0.0) -> Tensor:
+    """One nnhipActivationForward launch on the tape (also Tensor.log, autograd.py)."""
+    require_device_f32(x)
+    xd = contiguous(x.data)
+    f_x = x.xp.empty_like(xd)
+    call_hip_function("nnhipActivationForward", kind, f_x, xd, float(alpha), f_x.numel(), get_current_stream_ptr())
+    return _HIPActivationTensor(f_x, [x, kind, alpha], op, device=x.device)
+
+
+class HIPSoftplus(Module):
+    """neunet/nn/activations.py:140-160: log(1 + exp(x)), evaluated as max(x, 0) + log1p(exp(-|x|)) (finite above 88, relative
+    accuracy below -17 where the reference's float32 expression is inf / exactly 0); dx = dy sigmoid(x)."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_SOFTPLUS, "softplus")
+
+
+class HIPSoftsign(Module):
+    """neunet/nn/activations.py:174-194: x / (1 + |x|); dx = dy / (1 + |x|)^2."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_SOFTSIGN, "softsign")
+
+
+class HIPMish(Module):
+    """neunet/nn/activations.py:250-279: x tanh(softplus(x)); the derivative in the form t + x sigmoid(x) (1 - t^2), which has no
+    exp(3x) to overflow."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_MISH, "mish")
+
+
+class HIPTanhExp(Module):
+    """neunet/nn/activations.py:293-317: x tanh(exp(x)); dx = dy (t + x exp(x) (1 - t^2)), the second term dropped once 1 - t^2 is 0."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_TANHEXP, "tanh_exp")
+
+
+class HIPELU(Module):
+    """neunet/nn/activations.py:331-354, same constructor: x <= 0 ? alpha (exp(x) - 1) : x; the derivative at 0 is alpha."""
+
+    def __init__(self, alpha=0.1):
+        super().__init__()
+        self.alpha = alpha
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_ELU, "elu", self.alpha)
+
+
+class HIPSELU(Module):
+    """neunet/nn/activations.py:357-383: lambda (x > 0 ? x : alpha (exp(x) - 1)) with the reference's two constants (held by the
+    kernel; the attributes are informational)."""
+
+    def __init__(self):
+        super().__init__()
+        self.alpha = 1.6732632423543772848170429916717
+        self.lmbda = 1.0507009873554804934193349852946
+
+    def forward(self, x: Tensor):
+        return hip_activation(x, ACT_SELU, "selu")
 
 
 CUDASwish, CUDAFusedSwishAndMul, CUDASoftmax = HIPSwish, HIPFusedSwishAndMul, HIPSoftmax

@@ -8,6 +8,9 @@ path, all on the side of the CPU semantics (neunet/nn/losses.py:59-126):
   * ignored rows are excluded from the 'mean' denominator on the DEVICE (nnhipCountNotEqual), so the
     forward never synchronises the host (the reference calls `.item()`, cross_entropy.py:72);
   * the 'mean' / 'sum' reduction also runs on the device (nnhipReduceLoss).
+
+Also HIPBCELoss, HIPNLLLoss, HIPL1Loss and HIPKLDivLoss (neunet/nn/losses.py:25-56, 83-178): the CPU reference's constructors, loss and
+gradient from one launch each.
 """
 import weakref
 from ...autograd import Tensor
@@ -243,3 +246,186 @@ class HIPBCELoss(Module):
                           int(fold), get_current_stream_ptr())
         # fold: d(loss)/dz goes to the Sigmoid's input; the Sigmoid node drops out of this loss's backward
         return _HIPBCETensor(loss, (y_pred.args[0] if fold else y_pred, dpred), "bce", device="cuda")
+
+
+# ------------------------------------------------------------------------------------------------- NLLLoss
+class _HIPNLLTensor(Tensor):
+    """args = (y_pred, dlogp): the dense route -- the kernel's gradient with respect to the log-probabilities."""
+    _implicit_seed = True      # backward() with no argument needs no ones tensor: grad_fn below handles the unit seed
+
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+        out_ref = weakref.ref(self)
+
+        def grad_fn(y_pred: Tensor, dlogp, grad):
+            if getattr(out_ref(), "_seeded_with_ones", False):
+                y_pred.apply_grad(dlogp)
+                return
+            if getattr(grad, "ndim", 0) >= 1 and grad.numel() != 1:
+                # reduction 'none': one upstream value per position -- (N, 1) or the labels' shape -- against dlogp [N, C, d...]
+                grad = grad.reshape((dlogp.shape[0], 1) + tuple(dlogp.shape[2:]))
+            y_pred.apply_grad(times_upstream(dlogp, grad))
+
+        self.grad_fn = grad_fn
+
+
+class _HIPNLLFoldTensor(Tensor):
+    """args = (x, log_probs, labels, pos_grad): NLLLoss(LogSoftmax(x)) -- the node hangs on the LogSoftmax's INPUT and its backward is one
+    pass over the log-probabilities (nnhipLogSoftmaxNLLBackward); the dense [N, C] gradient of the NLL never exists."""
+    _implicit_seed = True
+
+    def __init__(self, data, args, op, device):
+        super().__init__(data, args, op, device=device, _nocopy=True)
+        out_ref = weakref.ref(self)
+
+        def grad_fn(x: Tensor, log_probs, labels, pos_grad, grad):
+            import torch
+            upstream = None
+            if not getattr(out_ref(), "_seeded_with_ones", False):
+                g = grad if isinstance(grad, torch.Tensor) else torch.as_tensor(grad, dtype=torch.float32, device=log_probs.device)
+                upstream = g.to(torch.float32).reshape(1).contiguous()
+            dx = torch.empty_like(log_probs)
+            rows, classes = log_probs.shape
+            call_hip_function("nnhipLogSoftmaxNLLBackward", dx, log_probs, labels, _LABEL_BYTES()[labels.dtype], pos_grad, upstream,
+                              rows, classes, get_current_stream_ptr())
+            x.apply_grad(dx)
+
+        self.grad_fn = grad_fn
+
+
+class HIPNLLLoss(Module):
+    """neunet/nn/losses.py:83-126, same constructor.  y_pred: log-probabilities (N, C) or (N, C, d1, ...), y_true: int16 / int32 / int64
+    class indices (N,) or (N, d1, ...).  loss = -y_pred[n, y, ...] * weight[y] per position, reduced by 'mean' (over the summed
+    weights of the counted positions), 'sum' or not at all ('none': shape (N, 1) for 2-D predictions with 1-D labels, the labels'
+    shape otherwise, as the reference returns).  Loss and gradient come from one launch (nnhipNLLLossForwardBackward); reduced losses
+    are 0-d.
+
+    Differences from the reference, on the side of nnhipCrossEntropyLossEx: a position whose label equals ignore_index is never
+    dereferenced (the reference indexes weight[y] before masking: its default ignore_index = -100 raises IndexError below 100
+    classes); a label outside [0, C) counts as nothing; a zero 'mean' denominator gives loss 0 and a zero gradient (reference: NaN).
+
+    NLLLoss(LogSoftmax(x)) with 2-D x, axis 1 and a reduced loss -- the reference's own CrossEntropyLoss, losses.py:66-77 -- folds the
+    two backward passes into one: the loss node hangs on x and nnhipLogSoftmaxNLLBackward writes dx from the log-probabilities and one
+    value per row.  Same loss bits as the dense route."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction="mean"):
+        super().__init__()
+        if reduction not in _RED:
+            raise ValueError("Reduction must be 'none', 'mean', or 'sum'")
+        self.reduction = reduction
+        self.ignore_index = ignore_index
+        self.weight = None
+        if weight is not None:
+            import numpy as np
+            w = weight.data if isinstance(weight, Tensor) else weight
+            if hasattr(w, "detach"):
+                w = w.detach().cpu().numpy()
+            self.weight = np.ascontiguousarray(np.asarray(w, dtype=np.float32))
+        self._weight_dev = None
+
+    def _device_weight(self, like):
+        import torch
+        if self.weight is None:
+            return None
+        if self._weight_dev is None or self._weight_dev.device != like.device:
+            self._weight_dev = torch.from_numpy(self.weight).to(like.device)
+        return self._weight_dev
+
+    def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
+        import torch
+        from .activations import _HIPLogSoftmaxTensor
+        if not isinstance(y_pred, Tensor) or not isinstance(y_true, Tensor):
+            raise TypeError("Input values must be tensors")
+        if y_pred.ndim < 2:
+            raise ValueError("Predictions must be (N, C) or (N, C, d1, ...)")
+        classes = y_pred.shape[1]
+        if self.weight is not None and tuple(self.weight.shape) != (classes,):      # losses.py:98-101, in the reference's order
+            raise ValueError("Weight shape must be equal to number of classes")
+        if y_true.dtype not in ("int16", "int32", "int64"):
+            raise TypeError("Target must be of int dtype")
+        if y_pred.device != "cuda" or y_true.device != "cuda":
+            raise ValueError("Tensors must be on the cuda (HIP) device")
+        if y_pred.dtype != "float32":
+            raise TypeError("Predictions must be of float32 dtype")
+        pshape, lshape = tuple(y_pred.shape), tuple(y_true.shape)
+        if lshape != (pshape[0],) + pshape[2:]:
+            raise ValueError(f"Target of shape {lshape} does not match predictions of shape {pshape}")
+        logp, labels = contiguous(y_pred.data), contiguous(y_true.data)
+        outer, inner = pshape[0], 1
+        for d in pshape[2:]:
+            inner *= d
+        none = self.reduction == "none"
+        fold = (not none and isinstance(y_pred, _HIPLogSoftmaxTensor) and len(pshape) == 2 and y_pred.args[2] % 2 == 1
+                and y_pred.args[0].requires_grad)
+        loss = torch.empty(((lshape[0], 1) if len(lshape) == 1 else lshape) if none else (), dtype=torch.float32, device=logp.device)
+        dlogp = None if fold else torch.empty_like(logp)
+        pos_grad = torch.empty(outer, dtype=torch.float32, device=logp.device) if fold else None
+        call_hip_function("nnhipNLLLossForwardBackward", logp, labels, _LABEL_BYTES()[labels.dtype], self._device_weight(logp),
+                          int(self.ignore_index), outer, classes, inner, _RED[self.reduction], loss, dlogp, pos_grad,
+                          get_current_stream_ptr())
+        if fold:
+            # d(loss)/dx goes to the LogSoftmax's input; the LogSoftmax node drops out of this loss's backward
+            return _HIPNLLFoldTensor(loss, (y_pred.args[0], logp, labels, pos_grad), "nll_log_softmax", device="cuda")
+        return _HIPNLLTensor(loss, (y_pred, dlogp), "nll", device="cuda")
+
+
+# ------------------------------------------------------------------------------------------------- L1Loss, KLDivLoss
+_RED_KL = dict(_RED, batchmean=b"b")
+
+
+class HIPL1Loss(Module):
+    """neunet/nn/losses.py:129-146, same constructor: |y_pred - y_true| reduced by 'mean', 'sum' or not at all ('none'); the gradient is
+    sign(y_pred - y_true) * scale with sign(0) = 0.  Loss and d(pred) come from one pass (nnhipL1LossForwardBackward); y_true receives
+    no gradient."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        if reduction not in _RED:
+            raise ValueError("Reduction must be 'none', 'mean', or 'sum'")
+        self.reduction = reduction
+
+    def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
+        import torch
+        if not isinstance(y_pred, Tensor) or not isinstance(y_true, Tensor):
+            raise TypeError("Input values must be tensors")
+        if y_pred.device != y_true.device:
+            raise ValueError("Tensors must be on the same device")
+        if y_pred.shape != y_true.shape:
+            raise ValueError("L1Loss on the HIP path needs equal shapes")
+        require_device_f32(y_pred, y_true)
+        p, t = contiguous(y_pred.data), contiguous(y_true.data)
+        none = self.reduction == "none"
+        loss = torch.empty(p.shape if none else (), dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p)
+        call_hip_function("nnhipL1LossForwardBackward", p, t, loss, dpred, p.numel(), _RED[self.reduction], get_current_stream_ptr())
+        return _HIPBCETensor(loss, (y_pred, dpred), "l1", device="cuda")
+
+
+class HIPKLDivLoss(Module):
+    """neunet/nn/losses.py:152-175, same constructor: y_true * (log(y_true) - y_pred), or with log_target exp(y_true) * (y_true - y_pred)
+    -- the reference's expression literally (a zero target gives NaN as np.log does) -- reduced by 'mean', 'batchmean' (sum / N),
+    'sum' or not at all ('none').  Loss and d(pred) come from one pass (nnhipKLDivLossForwardBackward); y_true receives no gradient."""
+
+    def __init__(self, reduction="mean", log_target=False):
+        super().__init__()
+        if reduction not in _RED_KL:
+            raise ValueError("Reduction must be 'none', 'mean', 'batchmean', or 'sum'")
+        self.reduction = reduction
+        self.log_target = log_target
+
+    def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
+        import torch
+        if not isinstance(y_pred, Tensor) or not isinstance(y_true, Tensor):
+            raise TypeError("Input values must be tensors")
+        if y_pred.device != y_true.device:
+            raise ValueError("Tensors must be on the same device")
+        if y_pred.shape != y_true.shape:
+            raise ValueError("KLDivLoss on the HIP path needs equal shapes")
+        require_device_f32(y_pred, y_true)
+        p, t = contiguous(y_pred.data), contiguous(y_true.data)
+        none = self.reduction == "none"
+        loss = torch.empty(p.shape if none else (), dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p)
+        call_hip_function("nnhipKLDivLossForwardBackward", p, t, loss, dpred, p.numel(), p.shape[0] if p.ndim else 1,
+                          int(bool(self.log_target)), _RED_KL[self.reduction], get_current_stream_ptr())
+        return _HIPBCETensor(loss, (y_pred, dpred), "kldiv", device="cuda")

@@ -1580,9 +1580,160 @@ def gen_optim_rules():
     save("mlp_optim_rules", **arrs)
 
 
+# --------------------------------------------------------------------------- the remaining activations and losses; word2vec
+def gen_activations_losses():
+    """act_*.npz (Softplus, Softsign, Mish, TanhExp, ELU at two alphas, SELU), logsoftmax_*.npz, log_tape.npz (Tensor.log), nll_*.npz,
+    l1_*.npz and kldiv_*.npz: the reference's values and gradients."""
+    seed_layers(130)
+    rng = np.random.default_rng(41)
+    X = (rng.standard_normal((8, 64)) * 2).astype(F32)
+    X[0, :4] = (0.0, -0.0, 10.0, -10.0)
+    dY = rng.standard_normal((8, 64)).astype(F32)
+    for tag, make, extra in [("softplus", nn.Softplus, {}), ("softsign", nn.Softsign, {}), ("mish", nn.Mish, {}),
+                             ("tanhexp", nn.TanhExp, {}), ("elu_a0.1", lambda: nn.ELU(0.1), {"alpha": np.float64(0.1)}),
+                             ("elu_a1.0", lambda: nn.ELU(1.0), {"alpha": np.float64(1.0)}), ("selu", nn.SELU, {})]:
+        x = T(X)
+        y = make()(x)
+        y.backward(dY)
+        save(f"act_{tag}", X=X, dY=dY, Y=y.data, dX=x.grad, **extra)
+
+    for tag, shape, axis in [("logsoftmax_last", (8, 64), -1), ("logsoftmax_axis1_4d", (2, 5, 3, 4), 1), ("logsoftmax_axis1_2d", (6, 50), 1)]:
+        Xs = (rng.standard_normal(shape) * 3).astype(F32)
+        dYs = rng.standard_normal(shape).astype(F32)
+        x = T(Xs)
+        y = nn.LogSoftmax(axis=axis)(x)
+        y.backward(dYs)
+        save(tag, X=Xs, dY=dYs, Y=y.data, dX=x.grad, axis=np.int64(axis))
+
+    Xl = rng.uniform(0.05, 4.0, (8, 64)).astype(F32)
+    x = T(Xl)
+    y = x.log()
+    y.backward(dY)
+    save("log_tape", X=Xl, dY=dY, Y=y.data, dX=x.grad)
+
+    # NLLLoss on the reference's LogSoftmax of a stored X: class weights, ignore_index = 0 (inside [0, C): the reference indexes
+    # weight[label] before it masks, so its default -100 raises IndexError below 100 classes) and at least one ignored label
+    for dims, shape in (("2d", (6, 50)), ("4d", (2, 5, 3, 4))):
+        C = shape[1]
+        Xn = (rng.standard_normal(shape) * 2).astype(F32)
+        labels = rng.integers(1, C, (shape[0],) + shape[2:]).astype(np.int32)
+        labels.reshape(-1)[[1, labels.size - 2]] = 0
+        W = rng.uniform(0.5, 2.0, C).astype(F32)
+        assert (labels == 0).sum() >= 1
+        for red in ("mean", "sum", "none"):
+            x = T(Xn)
+            lp = nn.LogSoftmax(axis=1)(x)
+            loss = nn.NLLLoss(weight=W, ignore_index=0, reduction=red)(lp, T(labels, dtype=np.int32, requires_grad=False))
+            loss.backward()
+            save(f"nll_{red}_{dims}", X=Xn, labels=labels, W=W, ignore_index=np.int64(0), logp=lp.data,
+                 loss=np.asarray(loss.data, np.float64), dlogp=lp.grad, dX=x.grad)
+
+    P = rng.uniform(-1.0, 1.0, (4, 5)).astype(F32)
+    Tg = rng.uniform(0.1, 1.0, (4, 5)).astype(F32)
+    assert not (P == Tg).any() and Tg.min() >= 0.1 and Tg.max() <= 1.0
+    for red in ("mean", "sum", "none"):
+        p = T(P)
+        loss = nn.L1Loss(reduction=red)(p, T(Tg, requires_grad=False))
+        loss.backward()
+        save(f"l1_{red}", P=P, Y=Tg, loss=np.asarray(loss.data, np.float64), dP=p.grad)
+    for red in ("mean", "batchmean", "sum", "none"):
+        for tag, log_target in (("lin", False), ("log", True)):
+            p = T(P)
+            loss = nn.KLDivLoss(reduction=red, log_target=log_target)(p, T(Tg, requires_grad=False))
+            loss.backward()
+            save(f"kldiv_{red}_{tag}", P=P, Y=Tg, loss=np.asarray(loss.data, np.float64), dP=p.grad, log_target=np.int64(log_target))
+
+
+W2V_TINY = {"words": 24, "hidden": 16, "steps": 3}       # the sonnet's first 24 words, hidden width 16 instead of 128: files under 100 KiB
+W2V_TINY_SEED = {"cbow": 0, "skipgram": 0}    # the first of 0, 1, 2, ... that meets _w2v_tiny_steps' conditions (--search-w2v-seed)
+W2V_PRE_FLOOR, W2V_PROB_FLOOR = 1e-4, 1e-6
+
+
+def _w2v_namespace():
+    """exec() cell 1 of /root/reference/examples/word2vec.ipynb (the text and the constants) and the two model classes of cells 2 and 3,
+    each cut before its training script, the hidden width replaced -- nothing of the notebook is copied into this repository."""
+    import json
+    nb = json.load(open("/root/reference/examples/word2vec.ipynb"))
+    ns = {"nn": nn, "nnet": neunet, "np": np, "print": lambda *a, **k: None}
+    exec("".join(nb["cells"][1]["source"]), ns)
+    for cell in (2, 3):
+        src = "".join(nb["cells"][cell]["source"])
+        src = src[:src.index("\n\nloss_function")]
+        assert src.count("128") == 2
+        exec(src.replace("128", str(W2V_TINY["hidden"])), ns)
+    return ns
+
+
+def w2v_pairs(words, context_size):
+    """The notebook's pairs over `words` with the vocabulary SORTED (the notebook's set order changes with the hash seed)."""
+    vocab = sorted(set(words))
+    ix = {w: i for i, w in enumerate(vocab)}
+    pairs = [([ix[words[i - j - 1]] for j in range(context_size)] + [ix[words[i + j + 1]] for j in range(context_size)], ix[words[i]])
+             for i in range(len(words) - context_size)]
+    return vocab, pairs
+
+
+def _w2v_tiny_steps(kind, seed):
+    seed_layers(1300 + seed)
+    ns = _w2v_namespace()
+    cs, dim = ns["CONTEXT_SIZE"], ns["EMBEDDING_DIM"]
+    vocab, pairs = w2v_pairs(ns["test_sentence"][:W2V_TINY["words"]], cs)
+    model = ns["CBOWModeler" if kind == "cbow" else "SkipGramModeler"](len(vocab), dim, cs)
+    named = [("E", model.embeddings.weight), ("W1", model.linear1.weight), ("b1", model.linear1.bias),
+             ("W2", model.linear2.weight), ("b2", model.linear2.bias)]
+    opt = Adam(model.parameters(), lr=0.001)
+    loss_fn = nn.NLLLoss()
+    arrs = {"cfg": np.array((len(vocab), dim, cs, W2V_TINY["hidden"], W2V_TINY["steps"]), np.int64)}
+    for n, p in named:
+        arrs[f"{n}_init"] = p.data.copy()
+    ok = True
+    for s in range(W2V_TINY["steps"]):
+        context, target = pairs[s]
+        ids, labels = (context, [target]) if kind == "cbow" else ([target], context)
+        ids, labels = np.array(ids, np.int16), np.array(labels, np.int16)
+        pre = model.embeddings.weight.data[ids].reshape(1, -1).astype(np.float64) @ model.linear1.weight.data.astype(np.float64).T \
+            + model.linear1.bias.data.astype(np.float64)
+        opt.zero_grad()
+        log_probs = model(neunet.tensor(ids, dtype=np.int16))
+        loss = loss_fn(log_probs, neunet.tensor(labels, dtype=np.int16, requires_grad=False))
+        loss.backward()
+        arrs.update({f"ids{s}": ids, f"labels{s}": labels, f"pre{s}": pre, f"logp{s}": log_probs.data.copy(),
+                     f"loss{s}": np.float64(loss.data)})
+        for n, p in named:
+            arrs[f"g{s}_{n}"] = p.grad.copy()
+        opt.step()
+        for n, p in named:
+            arrs[f"p{s}_{n}"] = p.data.copy()
+        ok = ok and w2v_conditions(pre, log_probs.data, labels)
+    return arrs, ok
+
+
+def w2v_conditions(pre, logp, labels):
+    """No linear1 pre-activation within 1e-4 of the ReLU kink, every probability at a label >= 1e-6."""
+    return bool(np.abs(pre).min() >= W2V_PRE_FLOOR and np.exp(logp[np.arange(len(labels)), labels]).min() >= W2V_PROB_FLOOR)
+
+
+def search_w2v_seed(kind, limit=400):
+    for seed in range(limit):
+        if _w2v_tiny_steps(kind, seed)[1]:
+            return seed
+    raise RuntimeError("no seed meets the conditions")
+
+
+def gen_word2vec():
+    """word2vec_{cbow,skipgram}.npz: three training steps of the notebook's two classes (one (context, target) pair per step, Adam
+    lr = 0.001, int16 ids) at a shrunken vocabulary and hidden width -- initial parameters, ids and labels, and per step the
+    log-probabilities, the loss, every gradient and every parameter after Adam."""
+    for kind in ("cbow", "skipgram"):
+        arrs, ok = _w2v_tiny_steps(kind, W2V_TINY_SEED[kind])
+        assert ok, f"the tiny {kind} steps miss their conditions (linear1 pre-activations off the ReLU kink, label probabilities >= 1e-6): --search-w2v-seed"
+        save(f"word2vec_{kind}", **arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
-              gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules]
+              gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules, gen_activations_losses,
+              gen_word2vec]
 
 
 def generate_all(out_dir=None, quiet=False):
@@ -1603,7 +1754,11 @@ if __name__ == "__main__":
     ap.add_argument("--search-gan-seed", action="store_true", help="print the first seed that meets gen_gan's conditions and stop")
     ap.add_argument("--search-vae-seed", action="store_true", help="print the first seed that meets gen_vae's conditions and stop")
     ap.add_argument("--search-vqvae-seed", action="store_true", help="print the first seed that meets gen_vq's conditions and stop")
+    ap.add_argument("--search-w2v-seed", action="store_true", help="print the first seeds that meet gen_word2vec's conditions and stop")
     a = ap.parse_args()
+    if a.search_w2v_seed:
+        print("W2V_TINY_SEED =", {k: search_w2v_seed(k) for k in ("cbow", "skipgram")})
+        sys.exit(0)
     if a.search_vqvae_seed:
         print("VQVAE_TINY_SEED =", search_vqvae_seed())
         sys.exit(0)

@@ -465,6 +465,82 @@ def main():
                 print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
                       f"round medians {' '.join(f'{v:.4f}' for v in m)}")
 
+    def alternate(title, routes, rounds=5, nbytes=None):
+        """The routes ALTERNATE in this process (`rounds` rounds each); per route the median of the round medians, the fastest launch,
+        and p10 - p90 of all timed launches.  nbytes: {route: algorithmic bytes}."""
+        samples, meds = {name: [] for name in routes}, {name: [] for name in routes}
+        for _ in range(rounds):
+            for name, fn in routes.items():
+                ms = bench_samples(fn, args.iters)
+                samples[name].extend(ms)
+                meds[name].append(float(np.median(ms)))
+        for name in routes:
+            allms, m = np.array(samples[name]), np.array(meds[name])
+            report(f"{name} {title}", float(np.median(m)), float(allms.min()), nbytes=(nbytes or {}).get(name))
+            print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches")
+
+    if "act" in only:
+        # Softplus, Softsign, Mish, TanhExp, ELU, SELU, log (nnhipActivationForward / Backward, csrc/elementwise.hip) beside nnhipTanhForward /
+        # Backward on the same 2^26 elements: the same map kernels and the same bytes (8 B / element forward, 12 backward), so a kind
+        # slower than Tanh is paying for its VALU work.
+        n = 1 << 26
+        X, dY, Y, dX = randn(n) * 2, randn(n), torch.empty(n, device=dev), torch.empty(n, device=dev)
+        Xp = X.abs() + 0.05
+        kinds = ("softplus", "softsign", "mish", "tanhexp", "elu", "selu", "log")
+        fwd = {"tanh": lambda: call("nnhipTanhForward", Y, X, n, st)}
+        bwd = {"tanh": lambda: call("nnhipTanhBackward", dX, dY, X, n, st)}
+        for k, name in enumerate(kinds):
+            src = Xp if name == "log" else X
+            fwd[name] = lambda k=k, src=src: call("nnhipActivationForward", k, Y, src, 0.1, n, st)
+            bwd[name] = lambda k=k, src=src: call("nnhipActivationBackward", k, dX, dY, src, 0.1, n, st)
+        alternate("fwd 2^26", fwd, nbytes={name: 8.0 * n for name in fwd})
+        alternate("bwd 2^26", bwd, nbytes={name: 12.0 * n for name in bwd})
+        del X, dY, Y, dX, Xp
+
+    if "logsoftmax" in only:
+        # nnhipLogSoftmaxForward / Backward beside nnhipSoftmaxForward / Backward (csrc/rowops.hip): the same tiers and the same bytes
+        for (rows, cols) in [(8192, 1024), (16384, 15000), (64, 50000)]:
+            X, dY, Y, dX = randn(rows, cols), randn(rows, cols), torch.empty(rows, cols, device=dev), torch.empty(rows, cols, device=dev)
+            fb, bb = 8.0 * rows * cols, 12.0 * rows * cols
+            alternate(f"fwd {rows}x{cols}", {"softmax": lambda: call("nnhipSoftmaxForward", Y, X, rows, cols, 1, st),
+                                             "logsoftmax": lambda: call("nnhipLogSoftmaxForward", Y, X, rows, cols, 1, st)},
+                      nbytes={"softmax": fb, "logsoftmax": fb})
+            call("nnhipLogSoftmaxForward", Y, X, rows, cols, 1, st)
+            alternate(f"bwd {rows}x{cols}", {"softmax": lambda: call("nnhipSoftmaxBackward", dX, dY, Y, rows, cols, 1, st),
+                                             "logsoftmax": lambda: call("nnhipLogSoftmaxBackward", dX, dY, Y, rows, cols, 1, st)},
+                      nbytes={"softmax": bb, "logsoftmax": bb})
+            del X, dY, Y, dX
+
+    if "nll" in only:
+        # The loss and backward of NLLLoss(LogSoftmax(x)) from the log-probabilities Y on: the fold (nnhipNLLLossForwardBackward with
+        # pos_grad only, then nnhipLogSoftmaxNLLBackward: Y read once, dX written once) beside the unfolded pair (the NLL entry with
+        # its dense gradient, then nnhipLogSoftmaxBackward: the dense gradient zero-filled and written, read back with Y, dX written --
+        # 5 streams of N C floats where the fold moves 2) and beside nnhipCrossEntropyLossEx from the logits (forward included: X read,
+        # the gradient written).
+        rows, cols = 16384, 15000
+        X = randn(rows, cols)
+        Y, dX, dlogp = torch.empty_like(X), torch.empty_like(X), torch.empty_like(X)
+        call("nnhipLogSoftmaxForward", Y, X, rows, cols, 1, st)
+        labels = torch.randint(0, cols, (rows,), device=dev, dtype=torch.int32, generator=g)
+        loss, pg = torch.empty((), device=dev), torch.empty(rows, device=dev)
+        loss_rows, lse, count = torch.empty(rows, device=dev), torch.empty(rows, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+
+        def fold():
+            call("nnhipNLLLossForwardBackward", Y, labels, 4, None, -100, rows, cols, 1, b"m", loss, None, pg, st)
+            call("nnhipLogSoftmaxNLLBackward", dX, Y, labels, 4, pg, None, rows, cols, st)
+
+        def pair():
+            call("nnhipNLLLossForwardBackward", Y, labels, 4, None, -100, rows, cols, 1, b"m", loss, dlogp, None, st)
+            call("nnhipLogSoftmaxBackward", dX, dlogp, Y, rows, cols, 1, st)
+
+        def fused_ce():
+            call("nnhipCrossEntropyLossEx", X, dX, loss_rows, lse, labels, 4, None, cols, -100, rows, cols, b"m", loss, count, st)
+
+        nc = 4.0 * rows * cols
+        alternate(f"{rows}x{cols}", {"fold": fold, "pair": pair, "crossentropy": fused_ce},
+                  nbytes={"fold": 2 * nc, "pair": 5 * nc, "crossentropy": 2 * nc})
+        del X, Y, dX, dlogp
+
     if want("conv"):
         for (B, Cin, H, Cout) in [(256, 1, 28, 8), (256, 8, 14, 16)]:
             X = rnd(B, Cin, H, H)
