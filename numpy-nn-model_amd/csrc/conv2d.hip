@@ -88,6 +88,12 @@ static int g_crq_n = 0;
 static hipStream_t g_crq_st = nullptr;
 static float* g_crq_arena = nullptr;
 static size_t g_crq_cap = 0, g_crq_used = 0;              // floats
+// The arena is reused from offset 0 after every flush, and the flushed reduce reads it on the stream it was launched on.  A job on
+// ANOTHER stream must not write its partials before that reduce is done: g_crq_reader is the stream of the last flushed reduce,
+// g_crq_writer the stream that has been ordered behind it (or is it).  Each new reader was itself ordered behind the one before.
+static hipStream_t g_crq_reader = nullptr, g_crq_writer = nullptr;
+static bool g_crq_read = false;                           // a reduce has been launched on g_crq_reader
+static hipEvent_t g_crq_ev = nullptr;
 
 static int crq_flush_locked(hipStream_t st) {
     if (g_crq_n == 0) return 0;
@@ -103,6 +109,8 @@ static int crq_flush_locked(hipStream_t st) {
     const int n = g_crq_n;
     g_crq_n = 0;
     g_crq_used = 0;
+    g_crq_reader = g_crq_writer = st;
+    g_crq_read = true;
     if (n == 1)
         hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grp.j[0].part, grp.j[0].dW, grp.j[0].db,
                            grp.j[0].chunks, grp.j[0].Cout, grp.j[0].Nw, grp.j[0].ncols);
@@ -121,6 +129,29 @@ void conv_reduce_cleanup() {
     g_crq_used = g_crq_cap = 0;
     if (g_crq_arena) (void)hipFree(g_crq_arena);
     g_crq_arena = nullptr;
+    if (g_crq_ev) (void)hipEventDestroy(g_crq_ev);
+    g_crq_ev = nullptr;
+    g_crq_read = false;
+}
+// Orders `st` behind the last flushed reduce (see g_crq_reader) before `st` may write the arena.  While `st` is being captured
+// nothing runs and nothing may be waited for (a wait or a query outside the graph would invalidate the capture): the launch is only
+// recorded, and whoever replays the graph orders the replay.  Otherwise an event; if the reader is itself being captured the arena is
+// not handed out (false: the caller takes the shared workspace and reduces at once).
+static bool crq_order_writer(hipStream_t st) {
+    if (!g_crq_read || st == g_crq_reader || st == g_crq_writer) return true;
+    hipStreamCaptureStatus cw = hipStreamCaptureStatusNone, cr = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cw);
+    if (cw != hipStreamCaptureStatusNone) return true;
+    if (g_crq_reader != nullptr) (void)hipStreamIsCapturing(g_crq_reader, &cr);   // (the null stream cannot be captured)
+    if (cr != hipStreamCaptureStatusNone) return false;
+    if (!g_crq_ev && hipEventCreateWithFlags(&g_crq_ev, hipEventDisableTiming) != hipSuccess) g_crq_ev = nullptr;
+    bool ok = g_crq_ev && hipEventRecord(g_crq_ev, g_crq_reader) == hipSuccess && hipStreamWaitEvent(st, g_crq_ev, 0) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ok = hipStreamSynchronize(g_crq_reader) == hipSuccess;
+    }
+    if (ok) g_crq_writer = st;
+    return ok;
 }
 // Where a weight-gradient kernel writes its `floats` partials: the arena when its reduce can wait for the flush (*deferred),
 // else the shared workspace (reduce launched at once).  nullptr: out of memory.
@@ -138,12 +169,13 @@ static float* conv_partials(size_t floats, hipStream_t st, bool* deferred, int* 
                 if (g_crq_arena) (void)hipFree(g_crq_arena);  // (synchronises: earlier reduces are done with it)
                 g_crq_arena = nullptr;
                 g_crq_cap = 0;
+                g_crq_read = false;
                 const size_t want = floats + (floats >> 1);
                 if (hipMalloc(&g_crq_arena, want * sizeof(float)) == hipSuccess) g_crq_cap = want;
                 else g_crq_arena = nullptr;
             }
         }
-        if (floats <= g_crq_cap - g_crq_used) {
+        if (floats <= g_crq_cap - g_crq_used && crq_order_writer(st)) {
             float* p = g_crq_arena + g_crq_used;
             g_crq_used += (floats + 63) & ~(size_t)63;
             g_crq_st = st;
@@ -625,7 +657,9 @@ __global__ __launch_bounds__(256) void conv_direct_dgrad_quad_kernel(const float
 // four positions): the four positions' taps reach a 4x4 patch of dO per channel (16 loads where four separate positions take
 // 36) and a weight read from LDS serves four positions -- the position-per-quad kernel above re-reads its 72 ds_read_b128 per
 // position and is LDS-bandwidth-bound at C5's second layer.  Same products in the same order per output (co = s, s + 4, ...; taps
-// in order; quad tree).
+// in order; quad tree) -- in the source: the compiler contracts every multiply-add here but leaves those of the other kernel's
+// channel groups co >= 8 as packed multiplies + additions, so above 8 output channels the two agree to rounding (measured: within
+// 2^-24 sum |a||b|), not bit for bit (tests/test_conv_tiers_gpu.py::test_quad2_against_quad; EXPERIMENTS.md 5.24).
 template <int CI>
 __global__ __launch_bounds__(256) void conv_direct_dgrad_quad2_kernel(const float* __restrict__ Wt, const float* __restrict__ dO,
                                                                       float* __restrict__ dX, const ConvGeom g) {
