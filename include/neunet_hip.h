@@ -713,6 +713,16 @@ int nnhipGaussianKLDForwardBackward(const float* mu, const float* logvar, float*
 #define NNHIP_ACT_ELU 4
 #define NNHIP_ACT_SELU 5
 #define NNHIP_ACT_LOG 6
+/* ABI 223, the unary maps of the Tensor tape (neunet/autograd.py:339-440, 588-602), the library functions literally:
+ *   NNHIP_ACT_EXP   exp(x)   f' = exp(x)          NNHIP_ACT_SQRT  sqrt(x)  f' = 0.5 / sqrt(x) (inf at 0, NaN below)
+ *   NNHIP_ACT_SIN   sin(x)   f' = cos(x)          NNHIP_ACT_COS   cos(x)   f' = -sin(x)
+ *   NNHIP_ACT_ABS   |x|      f' = sign(x) (0 at 0)
+ * Kind 7 is not assigned: it stays an unknown kind. */
+#define NNHIP_ACT_EXP 8
+#define NNHIP_ACT_SQRT 9
+#define NNHIP_ACT_SIN 10
+#define NNHIP_ACT_COS 11
+#define NNHIP_ACT_ABS 12
 int nnhipActivationForward(int kind, float* out, const float* in, float alpha, int64_t size, nnhipStream_t stream);
 int nnhipActivationBackward(int kind, float* dIn, const float* dOut, const float* in, float alpha, int64_t size,
                             nnhipStream_t stream);
@@ -1010,6 +1020,70 @@ int nnhipBidirectionalMergeForward(const float* D, const float* R, float* out, i
                                    nnhipStream_t stream);
 int nnhipBidirectionalMergeBackward(const float* grad, const float* D, const float* R, float* dD, float* dR, int64_t rows,
                                     int64_t hidden, int mode, nnhipStream_t stream);
+
+/* ---- the arithmetic core of the Tensor tape (ABI 223; neunet/autograd.py:96-531, 605-640) ---------------------------------------
+ * Shapes travel as `rank` (0..NNHIP_TENSOR_MAX_RANK) host int64 extents and per-operand host int64 strides in ELEMENTS, 0 along an
+ * axis the operand is broadcast over.  The entries drop axes of extent 1, merge adjacent axes every operand walks contiguously, and
+ * then allow at most 6 axis groups; the description reaches the kernels by value (no device upload: every entry may be captured).
+ * Status rules: a rank outside the limit, a negative extent, more than 6 groups, an unknown kind or a NULL required pointer is
+ * NNHIP_EINVAL, a pointer that is not 4-byte aligned NNHIP_EALIGN, a failed workspace request NNHIP_ENOMEM.  A zero-size tensor is a
+ * no-op.  No float atomics anywhere: reruns are bit-identical.  csrc/tensor_ops.hip describes the tiers.
+ *
+ * nnhipBroadcastBinaryForward: out[shape] (contiguous) = a (kind) b.  a or b (not both) may be NULL: that operand is `scalar`, by
+ *   value.  A one-element device tensor (all strides 0) is read on the device.  maximum / minimum propagate a NaN.
+ * nnhipBroadcastBinaryBackward: dA and / or dB (either may be NULL) from dOut[shape] (contiguous), the reference's expressions:
+ *   add (g, g)  sub (g, -g)  mul (g b, a g)  div (g / b, -g a / b^2)  power (g b a^(b-1), g a^b log a)
+ *   maximum (g (a >= b), g (a <= b))  minimum (g (a <= b), g (a >= b)).
+ *   dA is contiguous in a's OWN shape (extent 1 where stride_a is 0): the gradient of a broadcast operand is summed over its
+ *   broadcast axes inside the same launch, the full-shape gradient is never written.  One launch per gradient (two when the
+ *   reduced extent is split over blocks).  A by-value scalar has no gradient. */
+#define NNHIP_TENSOR_MAX_RANK 8
+#define NNHIP_BIN_ADD 0
+#define NNHIP_BIN_SUB 1
+#define NNHIP_BIN_MUL 2
+#define NNHIP_BIN_DIV 3
+#define NNHIP_BIN_POW 4
+#define NNHIP_BIN_MAX 5
+#define NNHIP_BIN_MIN 6
+int nnhipBroadcastBinaryForward(int kind, float* out, const float* a, const float* b, float scalar, int rank, const int64_t* shape,
+                                const int64_t* stride_a, const int64_t* stride_b, nnhipStream_t stream);
+int nnhipBroadcastBinaryBackward(int kind, float* dA, float* dB, const float* dOut, const float* a, const float* b, float scalar,
+                                 int rank, const int64_t* shape, const int64_t* stride_a, const int64_t* stride_b,
+                                 nnhipStream_t stream);
+/* nnhipReduceAxesForward: out (contiguous over the axes with reduce[i] == 0, in order) = the reduction of in[shape] (strides
+ *   `stride`) over the axes with reduce[i] != 0.  var is the population variance (ddof 0) from sums of (x - mean)^2, never
+ *   E[x^2] - E[x]^2; mean_out (var only, may be NULL) receives the means.  max / min propagate a NaN.  At most two launches; the
+ *   partials of a split reduction live in the library workspace (nnhipWorkspaceReserve before a capture).
+ * nnhipReduceAxesBackward: dX[shape] (contiguous) from grad (contiguous over the kept axes): sum g, mean g / n,
+ *   var g 2 (x - saved) / n with saved = the forward's means, max / min g (x == saved) with saved = the forward's output (every tie
+ *   receives g).  x and saved are not read for sum / mean.  One launch. */
+#define NNHIP_RED_SUM 0
+#define NNHIP_RED_MEAN 1
+#define NNHIP_RED_VAR 2
+#define NNHIP_RED_MAX 3
+#define NNHIP_RED_MIN 4
+int nnhipReduceAxesForward(int kind, float* out, float* mean_out, const float* in, int rank, const int64_t* shape,
+                           const int64_t* stride, const int32_t* reduce, nnhipStream_t stream);
+int nnhipReduceAxesBackward(int kind, float* dX, const float* grad, const float* x, const float* saved, int rank,
+                            const int64_t* shape, const int32_t* reduce, nnhipStream_t stream);
+/* out[shape] (contiguous) = scale * in (strides stride_in, 0 allowed): transpose / swapaxes and their backward.  A tile goes through
+ * LDS when `in` is contiguous along the second-to-last group of `out` (the 2-D-transpose pattern). */
+int nnhipStridedCopy(float* out, const float* in, float scale, int rank, const int64_t* shape, const int64_t* stride_in,
+                     nnhipStream_t stream);
+/* Test hook: the tier the most recent launch of the five entries above took (of the LAST launch of a call: for
+ * nnhipBroadcastBinaryBackward that is dB's when both gradients are asked for), and through `segments` (may be NULL) the number of
+ * segments a reduction split its reduced extent into (1: one launch, no finishing pass).  Not a status code. */
+#define NNHIP_TIER_NONE 0
+#define NNHIP_TIER_EW_SAME 1
+#define NNHIP_TIER_EW_SCALAR 2
+#define NNHIP_TIER_EW_VEC2D 3
+#define NNHIP_TIER_EW_GENERAL 4
+#define NNHIP_TIER_COPY_TILE 5
+#define NNHIP_TIER_RED_ROW_WAVE 10
+#define NNHIP_TIER_RED_ROW_BLOCK 11
+#define NNHIP_TIER_RED_COL 12
+#define NNHIP_TIER_RED_GENERAL 13
+int nnhipTensorOpsLastTier(int64_t* segments);
 
 #ifdef __cplusplus
 }

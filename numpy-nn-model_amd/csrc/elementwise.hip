@@ -6,106 +6,9 @@
 // kernel of the C3 pass (Swish forward) slower than Softmax forward on the same 268 MB (round-1 VERDICT).
 #include <stdlib.h>
 
-#include "common.h"
+#include "ew_map.h"
 
 namespace nnhip {
-
-constexpr int EW_THREADS = 256;
-constexpr int EW_MAX_BLOCKS = 1 << 20;  // one 4-float4 span per thread at any realistic size; the loop is a backstop
-
-inline int ew_blocks(int64_t n_items) {
-    int64_t b = ceil_div(n_items > 0 ? n_items : 1, EW_THREADS);
-    return (int)(b < EW_MAX_BLOCKS ? b : EW_MAX_BLOCKS);
-}
-
-// Generic unary/binary maps over float4 with scalar tail -----------------------------------------
-// Each block walks contiguous 256*EW_U-float4 spans; the EW_U loads of a span are issued together
-// (EW_U x 16 B in flight per lane) before any math, then EW_U stores.
-constexpr int EW_U = 4;
-
-typedef float ew_f4 __attribute__((ext_vector_type(4)));
-// Streaming accesses.  Non-temporal LOADS (bit 0, the default for tensors of >= 128 MB) read the inputs without allocating
-// in L2, which leaves L2 to the write-back of the previous kernel's output: cold C3 pass Swish forward 0.58-0.64 -> 0.74-0.78
-// of the HBM spec, backward 0.62 -> 0.69-0.77; back-to-back on hot buffers forward -4 %, backward +22 %.  Non-temporal
-// STORES (bit 1) win back-to-back (backward 6.8 TB/s) but lose cold (forward 0.58 -> 0.51) -- the consumer of an output is
-// usually the next kernel.  NNHIP_EW_NT overrides (developer switch).
-__device__ __forceinline__ float4 ew_load(const float4* p, int nt) {
-    if (nt & 1) { const ew_f4 t = __builtin_nontemporal_load(reinterpret_cast<const ew_f4*>(p)); return make_float4(t.x, t.y, t.z, t.w); }
-    return *p;
-}
-__device__ __forceinline__ void ew_store(float4* p, float4 v, int nt) {
-    if (nt & 2) { ew_f4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; __builtin_nontemporal_store(t, reinterpret_cast<ew_f4*>(p)); }
-    else *p = v;
-}
-static int ew_nt(int64_t n) {
-    static const int forced = []() { const char* e = getenv("NNHIP_EW_NT"); return e ? atoi(e) : -1; }();
-    if (forced >= 0) return forced;
-    return n * 4 >= ((int64_t)128 << 20) ? 1 : 0;
-}
-template <class F>
-__global__ __launch_bounds__(EW_THREADS) void map1_kernel(float* out, const float* a, int64_t n,
-                                                          bool vec, F f, int nt) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    if (vec) {
-        const int64_t nv = n >> 2;
-        const float4* a4 = reinterpret_cast<const float4*>(a);
-        float4* o4 = reinterpret_cast<float4*>(out);
-        for (int64_t base = (int64_t)blockIdx.x * (EW_THREADS * EW_U); base < nv; base += gsz * EW_U) {
-            float4 x[EW_U];
-#pragma unroll
-            for (int u = 0; u < EW_U; ++u) {
-                const int64_t i = base + u * EW_THREADS + threadIdx.x;
-                if (i < nv) x[u] = ew_load(a4 + i, nt);
-            }
-#pragma unroll
-            for (int u = 0; u < EW_U; ++u) {
-                const int64_t i = base + u * EW_THREADS + threadIdx.x;
-                if (i < nv) {
-                    float4 y;
-                    y.x = f(x[u].x); y.y = f(x[u].y); y.z = f(x[u].z); y.w = f(x[u].w);
-                    ew_store(o4 + i, y, nt);
-                }
-            }
-        }
-        for (int64_t i = (nv << 2) + gid; i < n; i += gsz) out[i] = f(a[i]);
-    } else {
-        for (int64_t i = gid; i < n; i += gsz) out[i] = f(a[i]);
-    }
-}
-
-template <class F>
-__global__ __launch_bounds__(EW_THREADS) void map2_kernel(float* out, const float* a, const float* b, int64_t n,
-                                                          bool vec, F f, int nt) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    if (vec) {
-        const int64_t nv = n >> 2;
-        const float4* a4 = reinterpret_cast<const float4*>(a);
-        const float4* b4 = reinterpret_cast<const float4*>(b);
-        float4* o4 = reinterpret_cast<float4*>(out);
-        for (int64_t base = (int64_t)blockIdx.x * (EW_THREADS * EW_U); base < nv; base += gsz * EW_U) {
-            float4 x[EW_U], z[EW_U];
-#pragma unroll
-            for (int u = 0; u < EW_U; ++u) {
-                const int64_t i = base + u * EW_THREADS + threadIdx.x;
-                if (i < nv) { x[u] = ew_load(a4 + i, nt); z[u] = ew_load(b4 + i, nt); }
-            }
-#pragma unroll
-            for (int u = 0; u < EW_U; ++u) {
-                const int64_t i = base + u * EW_THREADS + threadIdx.x;
-                if (i < nv) {
-                    float4 y;
-                    y.x = f(x[u].x, z[u].x); y.y = f(x[u].y, z[u].y); y.z = f(x[u].z, z[u].z); y.w = f(x[u].w, z[u].w);
-                    ew_store(o4 + i, y, nt);
-                }
-            }
-        }
-        for (int64_t i = (nv << 2) + gid; i < n; i += gsz) out[i] = f(a[i], b[i]);
-    } else {
-        for (int64_t i = gid; i < n; i += gsz) out[i] = f(a[i], b[i]);
-    }
-}
 
 // f = max(0, x)               (neunet/nn/activations.py:54-56: np.maximum propagates a NaN, fmaxf(NaN, 0) would return 0 and
 // hide a diverged activation from everything downstream): one unordered compare, `not (x <= 0)` is true for x > 0 and for NaN
@@ -225,32 +128,22 @@ struct SeluB {
 // Tensor.log (neunet/autograd.py:357): f = log(x), literally (log(0) = -inf, a negative x gives NaN) ; dx = dy / x
 struct LogF { __device__ float operator()(float x) const { return logf(x); } };
 struct LogB { __device__ float operator()(float dy, float x) const { return dy / x; } };
+// Tensor.exp / sqrt / sin / cos / abs (neunet/autograd.py:339-440, 610-626): the library functions, literally; every backward
+// functor reads the forward INPUT.  sqrt' is the reference's 0.5 x^-0.5 (inf at 0, NaN below), abs' is sign(x) (0 at 0, as np.sign)
+struct ExpF { __device__ float operator()(float x) const { return expf(x); } };
+struct ExpB { __device__ float operator()(float dy, float x) const { return dy * expf(x); } };
+struct SqrtF { __device__ float operator()(float x) const { return sqrtf(x); } };
+struct SqrtB { __device__ float operator()(float dy, float x) const { return dy * 0.5f / sqrtf(x); } };
+struct SinF { __device__ float operator()(float x) const { return sinf(x); } };
+struct SinB { __device__ float operator()(float dy, float x) const { return dy * cosf(x); } };
+struct CosF { __device__ float operator()(float x) const { return cosf(x); } };
+struct CosB { __device__ float operator()(float dy, float x) const { return dy * -sinf(x); } };
+struct AbsF { __device__ float operator()(float x) const { return fabsf(x); } };
+struct AbsB { __device__ float operator()(float dy, float x) const { return dy * (x > 0.f ? 1.f : (x < 0.f ? -1.f : (x == x ? 0.f : x))); } };
 struct ScaleF {
     float alpha;
     __device__ float operator()(float x) const { return alpha * x; }
 };
-struct AddF { __device__ float operator()(float a, float b) const { return a + b; } };
-struct MulF { __device__ float operator()(float a, float b) const { return a * b; } };
-
-template <class F>
-static int launch_map1(float* out, const float* a, int64_t n, F f, hipStream_t st, const char* nm) {
-    if (n == 0) return 0;
-    const bool vec = aligned16(out) && aligned16(a);
-    hipLaunchKernelGGL(map1_kernel<F>, dim3(ew_blocks(vec ? ceil_div(n >> 2, EW_U) : n)), dim3(EW_THREADS), 0, st,
-                       out, a, n, vec, f, ew_nt(n));
-    NNHIP_LAUNCH_CHECK(nm);
-    return 0;
-}
-template <class F>
-static int launch_map2(float* out, const float* a, const float* b, int64_t n, F f, hipStream_t st,
-                       const char* nm) {
-    if (n == 0) return 0;
-    const bool vec = aligned16(out) && aligned16(a) && aligned16(b);
-    hipLaunchKernelGGL(map2_kernel<F>, dim3(ew_blocks(vec ? ceil_div(n >> 2, EW_U) : n)), dim3(EW_THREADS), 0, st,
-                       out, a, b, n, vec, f, ew_nt(n));
-    NNHIP_LAUNCH_CHECK(nm);
-    return 0;
-}
 
 // SwiGLU gate.  in rows = [gate(h) | up(h)] (width 2h), out rows width h.
 // (fused_swish_and_mul.cu:13-57 semantics; oracle = Swish(gate)*up on the reference tape)
@@ -403,8 +296,10 @@ extern "C" int nnhipTanhBackward(float* dIn, const float* dOut, const float* out
     NNHIP_PTRS("nnhipTanhBackward", dIn, dOut, out);
     return launch_map2(dIn, dOut, out, size, TanhB{}, (hipStream_t)s, "tanh_backward");
 }
+// kinds 0..6 (ABI 222) and 8..12 (ABI 223: the Tensor maps); 7 is not assigned
+static bool act_kind_ok(int kind) { return (kind >= NNHIP_ACT_SOFTPLUS && kind <= NNHIP_ACT_LOG) || (kind >= NNHIP_ACT_EXP && kind <= NNHIP_ACT_ABS); }
 extern "C" int nnhipActivationForward(int kind, float* out, const float* in, float alpha, int64_t size, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(kind >= NNHIP_ACT_SOFTPLUS && kind <= NNHIP_ACT_LOG, NNHIP_EINVAL, "nnhipActivationForward: unknown kind %d", kind);
+    NNHIP_CHECK_ARG(act_kind_ok(kind), NNHIP_EINVAL, "nnhipActivationForward: unknown kind %d", kind);
     NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipActivationForward: negative size");
     if (size == 0) return 0;
     NNHIP_PTRS("nnhipActivationForward", out, in);
@@ -416,12 +311,17 @@ extern "C" int nnhipActivationForward(int kind, float* out, const float* in, flo
         case NNHIP_ACT_TANHEXP: return launch_map1(out, in, size, TanhExpF{}, st, "tanhexp_forward");
         case NNHIP_ACT_ELU: return launch_map1(out, in, size, EluF{alpha}, st, "elu_forward");
         case NNHIP_ACT_SELU: return launch_map1(out, in, size, SeluF{}, st, "selu_forward");
+        case NNHIP_ACT_EXP: return launch_map1(out, in, size, ExpF{}, st, "exp_forward");
+        case NNHIP_ACT_SQRT: return launch_map1(out, in, size, SqrtF{}, st, "sqrt_forward");
+        case NNHIP_ACT_SIN: return launch_map1(out, in, size, SinF{}, st, "sin_forward");
+        case NNHIP_ACT_COS: return launch_map1(out, in, size, CosF{}, st, "cos_forward");
+        case NNHIP_ACT_ABS: return launch_map1(out, in, size, AbsF{}, st, "abs_forward");
         default: return launch_map1(out, in, size, LogF{}, st, "log_forward");
     }
 }
 extern "C" int nnhipActivationBackward(int kind, float* dIn, const float* dOut, const float* in, float alpha, int64_t size,
                                        nnhipStream_t s) {
-    NNHIP_CHECK_ARG(kind >= NNHIP_ACT_SOFTPLUS && kind <= NNHIP_ACT_LOG, NNHIP_EINVAL, "nnhipActivationBackward: unknown kind %d", kind);
+    NNHIP_CHECK_ARG(act_kind_ok(kind), NNHIP_EINVAL, "nnhipActivationBackward: unknown kind %d", kind);
     NNHIP_CHECK_ARG(size >= 0, NNHIP_EINVAL, "nnhipActivationBackward: negative size");
     if (size == 0) return 0;
     NNHIP_PTRS("nnhipActivationBackward", dIn, dOut, in);
@@ -433,6 +333,11 @@ extern "C" int nnhipActivationBackward(int kind, float* dIn, const float* dOut, 
         case NNHIP_ACT_TANHEXP: return launch_map2(dIn, dOut, in, size, TanhExpB{}, st, "tanhexp_backward");
         case NNHIP_ACT_ELU: return launch_map2(dIn, dOut, in, size, EluB{alpha}, st, "elu_backward");
         case NNHIP_ACT_SELU: return launch_map2(dIn, dOut, in, size, SeluB{}, st, "selu_backward");
+        case NNHIP_ACT_EXP: return launch_map2(dIn, dOut, in, size, ExpB{}, st, "exp_backward");
+        case NNHIP_ACT_SQRT: return launch_map2(dIn, dOut, in, size, SqrtB{}, st, "sqrt_backward");
+        case NNHIP_ACT_SIN: return launch_map2(dIn, dOut, in, size, SinB{}, st, "sin_backward");
+        case NNHIP_ACT_COS: return launch_map2(dIn, dOut, in, size, CosB{}, st, "cos_backward");
+        case NNHIP_ACT_ABS: return launch_map2(dIn, dOut, in, size, AbsB{}, st, "abs_backward");
         default: return launch_map2(dIn, dOut, in, size, LogB{}, st, "log_backward");
     }
 }

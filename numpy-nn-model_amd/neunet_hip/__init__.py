@@ -390,3 +390,96 @@ def load(path):
     import pickle
     with open(path, "rb") as f:
         return pickle.load(f)
+
+
+# ---- the Tensor arithmetic as functions (neunet/__init__.py:152-246); device float32, see neunet_hip/tensor_ops.py ------------------
+def add(x, y):
+    return x + y
+
+
+def sub(x, y):
+    return x - y
+
+
+def mul(x, y):
+    return x * y
+
+
+def div(x, y):
+    return x / y
+
+
+def matmul(x, y):
+    return x.matmul(y)
+
+
+def sum(x, axis=None, keepdims=False):      # noqa: A001  (the reference's names)
+    return x.sum(axis=axis, keepdims=keepdims)
+
+
+def mean(x, axis=None, keepdims=False):
+    return x.mean(axis=axis, keepdims=keepdims)
+
+
+def var(x, axis=None, keepdims=False):
+    return x.var(axis=axis, keepdims=keepdims)
+
+
+def power(x, y):
+    return x ** y
+
+
+def sqrt(x):
+    return x.sqrt()
+
+
+def log(x):
+    return x.log()
+
+
+def exp(x):
+    return x.exp()
+
+
+def tanh(x):
+    return x.tanh()
+
+
+def sin(x):
+    return x.sin()
+
+
+def cos(x):
+    return x.cos()
+
+
+def maximum(x, y):
+    return x.maximum(y)
+
+
+def minimum(x, y):
+    return x.minimum(y)
+
+
+def max(x, axis=None, keepdims=False):      # noqa: A001
+    return x.max(axis=axis, keepdims=keepdims)
+
+
+def min(x, axis=None, keepdims=False):      # noqa: A001
+    return x.min(axis=axis, keepdims=keepdims)
+
+
+def reshape(x, *shape):
+    return x.reshape(*shape)
+
+
+def abs(x):                                 # noqa: A001
+    return x.abs()
+
+
+def transpose(x, *axes):
+    return x.transpose(*axes)
+
+
+def swapaxes(x, axis1, axis2):
+    return x.swapaxes(axis1, axis2)

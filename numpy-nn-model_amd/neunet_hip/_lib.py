@@ -244,6 +244,15 @@ _SIGNATURES = {
     "nnhipScale": (ctypes.c_int, [P, c_float, c_int64, c_void_p]),
     "nnhipScaleRows": (ctypes.c_int, [P, P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipAdd": (ctypes.c_int, [P, P, P, c_int64, c_void_p]),
+    "nnhipBroadcastBinaryForward": (ctypes.c_int, [ctypes.c_int, P, P, P, c_float, ctypes.c_int, POINTER(c_int64), POINTER(c_int64),
+                                                   POINTER(c_int64), c_void_p]),
+    "nnhipBroadcastBinaryBackward": (ctypes.c_int, [ctypes.c_int, P, P, P, P, P, c_float, ctypes.c_int, POINTER(c_int64), POINTER(c_int64),
+                                                    POINTER(c_int64), c_void_p]),
+    "nnhipReduceAxesForward": (ctypes.c_int, [ctypes.c_int, P, P, P, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
+                                              c_void_p]),
+    "nnhipReduceAxesBackward": (ctypes.c_int, [ctypes.c_int, P, P, P, P, ctypes.c_int, POINTER(c_int64), POINTER(c_int32), c_void_p]),
+    "nnhipStridedCopy": (ctypes.c_int, [P, P, c_float, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "nnhipTensorOpsLastTier": (ctypes.c_int, [POINTER(c_int64)]),
     "nnhipCommUniqueId": (ctypes.c_int, [ctypes.c_char_p]),
     "nnhipCommInitRank": (ctypes.c_int, [POINTER(c_void_p), ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "nnhipCommDestroy": (ctypes.c_int, [c_void_p]),
@@ -255,7 +264,7 @@ _SIGNATURES = {
 }
 _NO_STATUS = {"nnhipVersion", "nnhipLinearReLULinearBackwardFits", "nnhipBatchNorm2dLinearSigmoidMSEFits", "nnhipConv2dLeakyMaxPoolStatsBlocks", "nnhipGetLastErrorString", "nnhipCreateFusedOptimizer", "nnhipGetGemmMode", "nnhipGetGemmLockstep", "nnhipConv2dWeightGradPooledOk", "nnhipConv2dLeakyMaxPoolForwardOk", "nnhipGemmLaunchCount",
               "nnhipWeightGradPending", "nnhipGetLinearGemv", "nnhipSetConvTransposeRoute", "nnhipGetConvTransposeRoute",
-              "nnhipConvTranspose2dPlan"}
+              "nnhipConvTranspose2dPlan", "nnhipTensorOpsLastTier"}
 
 _dll = None
 _funcs: dict = {}

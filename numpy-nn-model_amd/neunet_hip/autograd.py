@@ -5,8 +5,10 @@ Restates the contract of neunet/autograd.py that the accelerated layers rely on 
   * apply_grad: reverse-broadcast then assign / accumulate-by-allocation  (autograd.py:85-93, 948-962)
   * backward: seed ones, DFS topological sort over `args`, replay `grad_fn(*args, grad=v.grad)`
     in reverse                                                        (autograd.py:965-1002)
-The ~45 elementwise/reduction ops of the reference Tensor are host NumPy glue and out of scope
-(SURVEY 2 #1); the few ops the hot-path callers need (reshape, add, log) are provided.
+The arithmetic core of the reference Tensor -- the broadcasting binary ops and their operators, the unary maps, the axis
+reductions, transpose / swapaxes / .T and matmul (autograd.py:96-531, 588-640, 810-893) -- runs on the device through
+tensor_ops.py (csrc/tensor_ops.hip); comparisons and logical ops, where, flip, __getitem__ / __setitem__ and integer
+tensors are not provided yet.
 
 Device arrays: on device "cuda" `Tensor.data` is a torch.Tensor living in HBM (torch-ROCm plays the
 role CuPy plays in the reference: allocation + streams only); on "cpu" it is a numpy.ndarray and the
@@ -325,28 +327,160 @@ class Tensor:
         out.grad_fn = grad_fn
         return out
 
-    def add(self, t: "Tensor") -> "Tensor":
-        """Residual add (neunet/autograd.py:96-116): out = self + t, both parents receive the gradient."""
-        if not isinstance(t, Tensor):
-            raise TypeError("only Tensor + Tensor is provided on the hot path")
-        if t.device != self.device:
-            raise ValueError("Tensors must be on the same device")
-        if tuple(t.shape) != tuple(self.shape):
-            raise ValueError("broadcasting adds are host glue and out of scope; shapes must match")
-        rg = self.requires_grad or t.requires_grad
-        out = Tensor(add_arrays(self.data, t.data), (self, t) if rg else None, "add", requires_grad=rg,
-                     device=self.device, _nocopy=True)
+    def add(self, t) -> "Tensor":
+        """out = self + t (neunet/autograd.py:96-116), both parents receive the gradient.  Same shape, contiguous, float32 is the residual
+        add of the hot path: one nnhipAdd.  Anything else on the device broadcasts (tensor_ops.binary); the same-shape CPU add stays."""
+        if isinstance(t, Tensor) and tuple(t.shape) == tuple(self.shape):
+            if t.device != self.device:
+                raise ValueError("Tensors must be on the same device")
+            rg = self.requires_grad or t.requires_grad
+            out = Tensor(add_arrays(self.data, t.data), (self, t) if rg else None, "add", requires_grad=rg,
+                         device=self.device, _nocopy=True)
 
-        def grad_fn(a, b, grad):
-            if a.requires_grad:
-                a.apply_grad(grad)
-            if b.requires_grad:
-                b.apply_grad(grad)
+            def grad_fn(a, b, grad):
+                if a.requires_grad:
+                    a.apply_grad(grad)
+                if b.requires_grad:
+                    b.apply_grad(grad)
 
-        out.grad_fn = grad_fn
-        return out
+            out.grad_fn = grad_fn
+            return out
+        if isinstance(t, Tensor):
+            if t.device != self.device:
+                raise ValueError("Tensors must be on the same device")
+            from .tensor_ops import broadcast_shape
+            broadcast_shape(self.shape, t.shape)        # ValueError when the shapes do not broadcast, on either device
+        return self._binary(t, "add")
+
+    def _binary(self, t, op, reflected=False):
+        from .tensor_ops import binary
+        return binary(self, t, op, reflected)
+
+    def sub(self, t) -> "Tensor":
+        return self._binary(t, "sub")
+
+    def mul(self, t) -> "Tensor":
+        return self._binary(t, "mul")
+
+    def div(self, t) -> "Tensor":
+        return self._binary(t, "div")
+
+    def power(self, t) -> "Tensor":
+        return self._binary(t, "power")
+
+    def maximum(self, t) -> "Tensor":
+        """NaN from either side propagates (np.maximum); on a tie both operands receive the gradient (autograd.py:456-460)."""
+        return self._binary(t, "maximum")
+
+    def minimum(self, t) -> "Tensor":
+        return self._binary(t, "minimum")
 
     __add__ = add
+    __sub__ = sub
+    __mul__ = mul
+    __truediv__ = div
+    __pow__ = power
+
+    def __radd__(self, t):
+        return self._binary(t, "add", reflected=True)
+
+    def __rsub__(self, t):
+        return self._binary(t, "sub", reflected=True)
+
+    def __rmul__(self, t):
+        return self._binary(t, "mul", reflected=True)
+
+    def __rtruediv__(self, t):
+        return self._binary(t, "div", reflected=True)
+
+    def __rpow__(self, t):
+        return self._binary(t, "power", reflected=True)
+
+    def __neg__(self):
+        from .tensor_ops import neg
+        return neg(self)
+
+    def __pos__(self):
+        from .tensor_ops import pos
+        return pos(self)
+
+    def matmul(self, t) -> "Tensor":
+        from .tensor_ops import matmul
+        return matmul(self, t)
+
+    __matmul__ = matmul
+
+    def __rmatmul__(self, t):
+        from .tensor_ops import matmul
+        return matmul(Tensor(np.asarray(t, dtype=np.float32), requires_grad=False, device=self.device), self)
+
+    __array_priority__ = 100
+    __array_ufunc__ = None          # a NumPy scalar or array on the left defers to the reflected operators
+
+    # ---- reductions (autograd.py:233-311, 490-531): axis None, an int or a tuple, negative axes, keepdims ------------------------
+    def _reduce(self, op, args, kwargs):
+        from .tensor_ops import reduce
+        axis = kwargs.pop("axis", None) if not args else args[0]
+        keepdims = kwargs.pop("keepdims", False) if len(args) < 2 else args[1]
+        if kwargs or len(args) > 2:
+            raise TypeError(f"Tensor.{op}: unsupported arguments {sorted(kwargs)}")
+        return reduce(self, op, axis, keepdims)
+
+    def sum(self, *args, **kwargs) -> "Tensor":
+        return self._reduce("sum", args, kwargs)
+
+    def mean(self, *args, **kwargs) -> "Tensor":
+        return self._reduce("mean", args, kwargs)
+
+    def var(self, *args, **kwargs) -> "Tensor":
+        """Population variance (ddof 0); the backward reuses the mean the forward computed."""
+        return self._reduce("var", args, kwargs)
+
+    def max(self, axis=None, keepdims=False) -> "Tensor":
+        """np.max: a NaN propagates; the backward is grad * (x == max) from the saved output, every tie receives the gradient."""
+        return self._reduce("max", (axis, keepdims), {})
+
+    def min(self, axis=None, keepdims=False) -> "Tensor":
+        return self._reduce("min", (axis, keepdims), {})
+
+    # ---- layout (autograd.py:605-640): contiguous results, the backward is the inverse permutation ---------------------------------
+    def transpose(self, *axes) -> "Tensor":
+        from .tensor_ops import transpose
+        axes = axes[0] if len(axes) == 1 and not isinstance(axes[0], (int, np.integer)) else axes
+        return transpose(self, tuple(axes) if axes is not None else ())
+
+    def swapaxes(self, axis1: int, axis2: int) -> "Tensor":
+        from .tensor_ops import swapaxes
+        return swapaxes(self, axis1, axis2)
+
+    @property
+    def T(self) -> "Tensor":
+        return self.transpose()
+
+    # ---- unary maps (autograd.py:339-440, 588-602) -----------------------------------------------------------------------------------
+    def exp(self) -> "Tensor":
+        from .tensor_ops import ACT_EXP, unary
+        return unary(self, ACT_EXP, "exp")
+
+    def sqrt(self) -> "Tensor":
+        from .tensor_ops import ACT_SQRT, unary
+        return unary(self, ACT_SQRT, "sqrt")
+
+    def sin(self) -> "Tensor":
+        from .tensor_ops import ACT_SIN, unary
+        return unary(self, ACT_SIN, "sin")
+
+    def cos(self) -> "Tensor":
+        from .tensor_ops import ACT_COS, unary
+        return unary(self, ACT_COS, "cos")
+
+    def abs(self) -> "Tensor":
+        from .tensor_ops import ACT_ABS, unary
+        return unary(self, ACT_ABS, "abs")
+
+    def tanh(self) -> "Tensor":
+        from .tensor_ops import tanh
+        return tanh(self)
 
     def log(self) -> "Tensor":
         """Natural logarithm on the tape (neunet/autograd.py:357): out = log(self), literally (log(0) = -inf, a negative entry gives

@@ -1730,10 +1730,155 @@ def gen_word2vec():
         save(f"word2vec_{kind}", **arrs)
 
 
+def tape_cases():
+    """{tag: (input names, function of reference Tensors)}: the single ops and the compositions of gen_tape_ops.  The inputs' shapes
+    and the positivity a case needs are in TAPE_INPUTS."""
+    c = {}
+    for op in ("add", "sub", "mul", "div", "power", "maximum", "minimum"):
+        c[f"{op}_row"] = (("A", "bF"), lambda a, b, op=op: getattr(a, op)(b))           # [N,F] o [F]
+        c[f"{op}_col"] = (("A", "cN"), lambda a, b, op=op: getattr(a, op)(b))           # [N,F] o [N,1]
+        c[f"{op}_rcol"] = (("cN", "A"), lambda a, b, op=op: getattr(a, op)(b))          # the small operand on the left
+    c["scalars"] = (("A",), lambda a: (2.0 - a) * 0.5 + 1.5 / (a + 3.0) - a ** 2 + 2.0 ** a + (-a))
+    for op in ("exp", "sqrt", "sin", "cos", "abs", "tanh"):
+        c[op] = (("A",), lambda a, op=op: getattr(a, op)())
+    for op in ("sum", "mean", "var", "max", "min"):
+        c[f"{op}_all"] = (("X",), lambda x, op=op: getattr(x, op)())
+        c[f"{op}_ax1"] = (("X",), lambda x, op=op: getattr(x, op)(axis=1))
+        c[f"{op}_ax02k"] = (("X",), lambda x, op=op: getattr(x, op)(axis=(0, 2), keepdims=True))
+        c[f"{op}_last"] = (("X",), lambda x, op=op: getattr(x, op)(axis=-1, keepdims=True))
+    # (the reference's backward applies the SAME permutation again: only self-inverse permutations are fixtures)
+    c["transpose"] = (("X",), lambda x: x.transpose(0, 2, 1))
+    c["swapaxes"] = (("X",), lambda x: x.swapaxes(0, 2))
+    c["T"] = (("A",), lambda a: a.T)
+    c["matmul_mm"] = (("A", "W"), lambda a, w: a @ w)
+    c["matmul_batched"] = (("P", "Q"), lambda p, q: p @ q)
+    c["matmul_shared"] = (("P", "W7"), lambda p, w: p @ w)
+    c["matmul_vv"] = (("bF", "vF"), lambda a, b: a @ b)
+    c["matmul_vm"] = (("bF", "W"), lambda a, w: a @ w)
+    c["matmul_mv"] = (("A", "vF"), lambda a, v: a @ v)
+    c["layernorm"] = (("A", "bF", "vF"), lambda x, w, b: (x - x.mean(-1, keepdims=True)) / (x.var(-1, keepdims=True) + 1e-5).sqrt() * w + b)
+    c["softmax"] = (("A",), lambda x: (x - x.max(axis=1, keepdims=True)).exp() / (x - x.max(axis=1, keepdims=True)).exp().sum(axis=1, keepdims=True))
+    c["mse"] = (("A", "A2"), lambda a, b: ((a - b) ** 2).mean())
+    c["linear_tanh_sum"] = (("A", "W", "b3"), lambda x, w, b: (x @ w + b).tanh().sum(axis=0))
+    c["twice"] = (("A", "bF"), lambda a, b: a * b + a / (b * b + 1.0) + a)
+    return c
+
+
+TAPE_INPUTS = {"A": (4, 5), "A2": (4, 5), "bF": (5,), "vF": (5,), "cN": (4, 1), "X": (3, 4, 5), "W": (5, 3), "b3": (3,), "P": (2, 3, 5, 7),
+               "Q": (2, 3, 7, 4), "W7": (7, 4)}
+TAPE_POSITIVE = ("div", "power", "sqrt")        # cases whose operands are drawn from [0.5, 2.5): no pole, no negative base
+
+
+def gen_tape_ops():
+    """tape_ops.npz: every op of the Tensor arithmetic and five compositions on the reference's tape -- per case the inputs, the
+    output, an upstream gradient and every input's gradient ("<case>/in<i>", "/Y", "/dY", "/d<i>")."""
+    rng = np.random.default_rng(223)
+    arrs = {}
+    for tag, (names, fn) in tape_cases().items():
+        pos = tag.split("_")[0] in TAPE_POSITIVE
+        ins = [(rng.uniform(0.5, 2.5, TAPE_INPUTS[n]) if pos else rng.standard_normal(TAPE_INPUTS[n])).astype(F32) for n in names]
+        ts = [T(a) for a in ins]
+        y = fn(*ts)
+        dY = rng.standard_normal(np.shape(y.data)).astype(F32)
+        y.backward(dY)
+        arrs[f"{tag}/Y"], arrs[f"{tag}/dY"] = np.asarray(y.data, F32), dY
+        for i, (a, t) in enumerate(zip(ins, ts)):
+            arrs[f"{tag}/in{i}"], arrs[f"{tag}/d{i}"] = a, np.asarray(t.grad, F32).reshape(a.shape)
+    save("tape_ops", **arrs)
+
+
+def _conway_namespace():
+    """exec() cells 3-5 of /root/reference/examples/conway.ipynb (GameOfLife, Dataset, Net) from their place -- nothing of the notebook
+    is copied into this repository."""
+    import itertools
+    import json
+    nb = json.load(open("/root/reference/examples/conway.ipynb"))
+    ns = {"nn": nn, "neunet": neunet, "np": np, "itertools": itertools}
+    for cell in (3, 4, 5):
+        exec("".join(nb["cells"][cell]["source"]), ns)
+    return ns
+
+
+CONWAY_STEPS = 3
+CONWAY_CASES = (150, 311, 427)      # three of the 512 neighbourhoods, live and dead centres
+CONWAY_RUN = {"seed": 0, "epochs": 8}       # --search-conway-seed: the first seed whose short run the conditions below accept
+CONWAY_MAX_EPOCHS, CONWAY_MARGIN = 12, 0.15
+
+
+def _conway_model(ns, seed):
+    """(model, its named parameters): Net drawn from the global generator seeded for `seed` (after the game's own layer was built)."""
+    seed_layers(1400 + seed)
+    model = ns["Net"]()
+    return model, [("W1", model.conv1.weight), ("b1", model.conv1.bias), ("W2", model.conv2.weight), ("b2", model.conv2.bias)]
+
+
+def _conway_run(ns, X, Y, seed, epochs):
+    """The notebook's training loop (cell 7: one neighbourhood per step, MSELoss, Adam lr 0.01) for `epochs` epochs, each epoch a
+    fresh permutation from default_rng(seed) -> per epoch (cases of the 512 the rounded net gets wrong, the smallest distance of a
+    prediction from the 0.5 threshold)."""
+    model, _ = _conway_model(ns, seed)
+    opt, criterion, rng, out = Adam(model.parameters(), lr=0.01), nn.MSELoss(), np.random.default_rng(seed), []
+    for _ in range(epochs):
+        for i in rng.permutation(len(X)):
+            opt.zero_grad()
+            x = neunet.tensor(np.pad(X[i], pad_width=1, mode="wrap"))[None, None, :, :]
+            loss = criterion(model(x), neunet.tensor(Y[i])[None, None, :, :])
+            loss.backward()
+            opt.step()
+        preds = np.array([model(neunet.tensor(np.pad(x, pad_width=1, mode="wrap"))[None, None, :, :]).data[0, 0] for x in X])
+        out.append((int(((preds > 0.5).astype(int) != Y).any(axis=(1, 2)).sum()), float(np.abs(preds - 0.5).min())))
+    return out
+
+
+def search_conway_seed(limit=20):
+    """The first (seed, epochs) with epochs <= CONWAY_MAX_EPOCHS after which the reference's net gets none of the 512 cases wrong and
+    no prediction is closer than CONWAY_MARGIN to the threshold (so that a float32 trajectory a few ulp away rounds the same)."""
+    ns = _conway_namespace()
+    X, Y = ns["Dataset"]().get_data(ns["GameOfLife"]())
+    for seed in range(limit):
+        for epoch, (wrong, margin) in enumerate(_conway_run(ns, X, Y, seed, CONWAY_MAX_EPOCHS)):
+            if wrong == 0 and margin >= CONWAY_MARGIN:
+                return {"seed": seed, "epochs": epoch + 1}
+    raise RuntimeError("no seed meets the conditions")
+
+
+def gen_conway():
+    """conway_steps.npz: the 512-case dataset of the notebook (X, Y), Net's initial parameters, three training steps (one
+    neighbourhood each, MSELoss, Adam lr 0.01 as in cell 6): per step the prediction, the loss, every gradient and every parameter
+    after Adam -- and the short run CONWAY_RUN from the same initial parameters: its seed and epoch count, and per epoch how many of
+    the 512 cases the reference's trained net gets wrong and its margin to the threshold (0 wrong at the end, by the search)."""
+    ns = _conway_namespace()
+    X, Y = ns["Dataset"]().get_data(ns["GameOfLife"]())
+    model, named = _conway_model(ns, CONWAY_RUN["seed"])
+    arrs = {"X": X.astype(np.int8), "Y": Y.astype(np.int8), "cases": np.array(CONWAY_CASES, np.int64)}
+    for n, p in named:
+        arrs[f"{n}_init"] = np.asarray(p.data, F32).copy()
+    opt = Adam(model.parameters(), lr=0.01)
+    criterion = nn.MSELoss()
+    for s, i in enumerate(CONWAY_CASES[:CONWAY_STEPS]):
+        opt.zero_grad()
+        x = neunet.tensor(np.pad(X[i], pad_width=1, mode="wrap"))[None, None, :, :]
+        y = neunet.tensor(Y[i])[None, None, :, :]
+        y_pred = model(x)
+        loss = criterion(y_pred, y)
+        loss.backward()
+        arrs[f"pred{s}"], arrs[f"loss{s}"] = np.asarray(y_pred.data, F32).copy(), np.float64(loss.data)
+        for n, p in named:
+            arrs[f"g{s}_{n}"] = np.asarray(p.grad, F32).reshape(p.data.shape).copy()
+        opt.step()
+        for n, p in named:
+            arrs[f"p{s}_{n}"] = np.asarray(p.data, F32).copy()
+    run = _conway_run(ns, X, Y, CONWAY_RUN["seed"], CONWAY_RUN["epochs"])
+    assert run[-1][0] == 0 and run[-1][1] >= CONWAY_MARGIN, f"the short run misses its conditions {run[-1]}: --search-conway-seed"
+    arrs.update(run_seed=np.int64(CONWAY_RUN["seed"]), run_epochs=np.int64(CONWAY_RUN["epochs"]),
+                run_wrong=np.array([w for w, _ in run], np.int64), run_margin=np.array([m for _, m in run], np.float64))
+    save("conway_steps", **arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
               gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules, gen_activations_losses,
-              gen_word2vec]
+              gen_word2vec, gen_tape_ops, gen_conway]
 
 
 def generate_all(out_dir=None, quiet=False):
@@ -1754,8 +1899,12 @@ if __name__ == "__main__":
     ap.add_argument("--search-gan-seed", action="store_true", help="print the first seed that meets gen_gan's conditions and stop")
     ap.add_argument("--search-vae-seed", action="store_true", help="print the first seed that meets gen_vae's conditions and stop")
     ap.add_argument("--search-vqvae-seed", action="store_true", help="print the first seed that meets gen_vq's conditions and stop")
+    ap.add_argument("--search-conway-seed", action="store_true", help="print the first seed and epoch count that meet gen_conway's conditions and stop")
     ap.add_argument("--search-w2v-seed", action="store_true", help="print the first seeds that meet gen_word2vec's conditions and stop")
     a = ap.parse_args()
+    if a.search_conway_seed:
+        print("CONWAY_RUN =", search_conway_seed())
+        sys.exit(0)
     if a.search_w2v_seed:
         print("W2V_TINY_SEED =", {k: search_w2v_seed(k) for k in ("cbow", "skipgram")})
         sys.exit(0)

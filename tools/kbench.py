@@ -497,6 +497,64 @@ def main():
         alternate("bwd 2^26", bwd, nbytes={name: 12.0 * n for name in bwd})
         del X, dY, Y, dX, Xp
 
+    if "tape" in only:
+        # The Tensor arithmetic (csrc/tensor_ops.hip): same-shape mul / div beside nnhipMul; the inner-row and outer-column broadcasts
+        # beside the same-shape kernel on the same output bytes and beside the torch expression; row / column / NCHW-channel reductions
+        # beside torch.sum (algorithmic bytes: the input once); the fused broadcast backward (dB of a * b without the full-shape
+        # gradient) beside the unfused pair (nnhipMul into a full-shape buffer, then the reduction).
+        import ctypes
+
+        def i64(*v):
+            return (ctypes.c_int64 * len(v))(*v)
+
+        def i32(*v):
+            return (ctypes.c_int32 * len(v))(*v)
+
+        n = 1 << 26
+        A, B, O = randn(n), randn(n).abs() + 0.5, torch.empty(n, device=dev)
+        sh, s1 = i64(n), i64(1)
+        alternate("same 2^26", {"nnhipMul": lambda: call("nnhipMul", O, A, B, n, st),
+                                "mul": lambda: call("nnhipBroadcastBinaryForward", 2, O, A, B, 0.0, 1, sh, s1, s1, st),
+                                "div": lambda: call("nnhipBroadcastBinaryForward", 3, O, A, B, 0.0, 1, sh, s1, s1, st),
+                                "mul scalar": lambda: call("nnhipBroadcastBinaryForward", 2, O, A, None, 0.5, 1, sh, s1, s1, st)},
+                  nbytes={"nnhipMul": 12.0 * n, "mul": 12.0 * n, "div": 12.0 * n, "mul scalar": 8.0 * n})
+        del A, B, O
+        N, F = 16384, 4096
+        X, X2, row, col, O = randn(N, F), randn(N, F), randn(F), randn(N, 1), torch.empty(N, F, device=dev)
+        sh2, full, srow, scol = i64(N, F), i64(F, 1), i64(0, 1), i64(1, 0)
+        alternate(f"[{N},{F}] mul", {"same": lambda: call("nnhipBroadcastBinaryForward", 2, O, X, X2, 0.0, 2, sh2, full, full, st),
+                                     "inner [F]": lambda: call("nnhipBroadcastBinaryForward", 2, O, X, row, 0.0, 2, sh2, full, srow, st),
+                                     "outer [N,1]": lambda: call("nnhipBroadcastBinaryForward", 2, O, X, col, 0.0, 2, sh2, full, scol, st),
+                                     "torch inner": lambda: torch.mul(X, row, out=O), "torch outer": lambda: torch.mul(X, col, out=O)},
+                  nbytes={"same": 12.0 * N * F, "inner [F]": 8.0 * N * F, "outer [N,1]": 8.0 * N * F, "torch inner": 8.0 * N * F,
+                          "torch outer": 8.0 * N * F})
+        orow, ocol = torch.empty(N, device=dev), torch.empty(F, device=dev)
+        alternate(f"[{N},{F}] sum", {"axis 1": lambda: call("nnhipReduceAxesForward", 0, orow, None, X, 2, sh2, full, i32(0, 1), st),
+                                     "axis 0": lambda: call("nnhipReduceAxesForward", 0, ocol, None, X, 2, sh2, full, i32(1, 0), st),
+                                     "var axis 1": lambda: call("nnhipReduceAxesForward", 2, orow, None, X, 2, sh2, full, i32(0, 1), st),
+                                     "torch axis 1": lambda: torch.sum(X, 1, out=orow), "torch axis 0": lambda: torch.sum(X, 0, out=ocol)},
+                  nbytes={k: 4.0 * N * F for k in ("axis 1", "axis 0", "var axis 1", "torch axis 1", "torch axis 0")})
+        G = randn(N, F)
+        drow, dcol = torch.empty(F, device=dev), torch.empty(N, 1, device=dev)
+
+        def unfused(dst, axis):
+            call("nnhipMul", O, G, X, N * F, st)
+            call("nnhipReduceAxesForward", 0, dst, None, O, 2, sh2, full, i32(*axis), st)
+
+        alternate(f"[{N},{F}] dB of a*b", {"fused [F]": lambda: call("nnhipBroadcastBinaryBackward", 2, None, drow, G, X, row, 0.0, 2, sh2, full, srow, st),
+                                           "unfused [F]": lambda: unfused(drow, (1, 0)),
+                                           "fused [N,1]": lambda: call("nnhipBroadcastBinaryBackward", 2, None, dcol, G, X, col, 0.0, 2, sh2, full, scol, st),
+                                           "unfused [N,1]": lambda: unfused(dcol, (0, 1))},
+                  nbytes={"fused [F]": 8.0 * N * F, "unfused [F]": 16.0 * N * F, "fused [N,1]": 8.0 * N * F, "unfused [N,1]": 16.0 * N * F})
+        del X, X2, O, G
+        shp = (64, 256, 56, 56)
+        X4, oc = randn(*shp), torch.empty(256, device=dev)
+        alternate("[64,256,56,56] sum (0,2,3)", {"general tier": lambda: call("nnhipReduceAxesForward", 0, oc, None, X4, 4, i64(*shp),
+                                                                                i64(256 * 3136, 3136, 56, 1), i32(1, 0, 1, 1), st),
+                                                 "torch": lambda: torch.sum(X4, (0, 2, 3), out=oc)},
+                  rounds=2, nbytes={"general tier": 4.0 * X4.numel(), "torch": 4.0 * X4.numel()})
+        del X4
+
     if "logsoftmax" in only:
         # nnhipLogSoftmaxForward / Backward beside nnhipSoftmaxForward / Backward (csrc/rowops.hip): the same tiers and the same bytes
         for (rows, cols) in [(8192, 1024), (16384, 15000), (64, 50000)]:
