@@ -1,5 +1,6 @@
 """CPU-only tests of ConvTranspose2d: the float64 restatement (tests/convtranspose_ref.py) against the reference's recorded
-outputs and against torch, the host-only plan and the C ABI's argument checks (no device call is made), and the host module."""
+outputs and against torch, the host-only plan and the C ABI's argument checks (no device call is made), the host module, and what
+the tier table of convtranspose_ref.py reaches in csrc/conv_transpose.hip and csrc/conv_mfma.hip."""
 import ctypes
 
 import numpy as np
@@ -63,11 +64,15 @@ def test_restatement_matches_reference_fixture(golden, name):
     np.testing.assert_allclose(db, f["db"].reshape(-1), rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("name", sorted(R.GEOMETRIES) + ["big"])
+def geometry(name):
+    return BIG if name == "big" else R.GEOMETRIES[name] if name in R.GEOMETRIES else R.TIER_CASES[name]
+
+
+@pytest.mark.parametrize("name", sorted(R.GEOMETRIES) + ["big"] + sorted(R.TIER_CASES))
 def test_restatement_matches_torch_float64(name):
     """= torch conv_transpose2d(X, W.flip(2, 3).transpose(0, 1), ...); a 4-tuple padding is the zero-padding result cropped."""
     import torch.nn.functional as F
-    g, X, W, b, dO = R.make_case(BIG if name == "big" else R.GEOMETRIES[name], 5)
+    g, X, W, b, dO = R.make_case(geometry(name), 5)
     t = lambda a: torch.tensor(a, dtype=torch.float64, requires_grad=True)   # noqa: E731
     Xt, Wt, bt = t(X), t(W), t(b)
     # torch wants padding <= d (k-1) + ... and symmetric: run it unpadded, with the output padding the crop leaves room for
@@ -118,7 +123,99 @@ def test_plan_routes_of_the_fixture_table():
     assert routes["convt_dil_gcd"] == routes["convt_s3k2"] == routes["convt_mixed"] == routes["convt_uneven"] == ROUTE_GATHER
 
 
-# ---- ABI edges (no device work: argument checks come first) --------------------------------------------------------------------
+# ---- the tier table (convtranspose_ref.TIER_CASES) -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(R.TIER_CASES))
+def test_tier_plan_matches_brute_force(name):
+    """nnhipConvTranspose2dPlan per phase = the brute-force counts = the restated phase_axis / phase_taps; `auto` = the restated
+    resolve_route; the bias-only pixels the GPU tests look at are the pixels no tap divides into."""
+    _load()
+    g = R.normalise(R.TIER_CASES[name])
+    rc, route, taps, pixels = plan(make_desc(g))
+    assert rc == g["sh"] * g["sw"]
+    bt, bp = R.phase_tap_pixel_counts(g)
+    assert taps == bt and pixels == bp
+    assert sum(t * p for t, p in zip(taps, pixels)) == R.tap_pixel_pairs(g)
+    fp = R.forward_plan(g)
+    assert [p["taps"] for p in fp["phases"]] == taps and [p["pixels"] for p in fp["phases"]] == pixels
+    assert route == R.auto_route(g)
+    none = np.array([[not any((y + g["pu"] - r * g["dh"]) % g["sh"] == 0 for r in range(g["kh"])) or
+                      not any((x + g["pl"] - s * g["dw"]) % g["sw"] == 0 for s in range(g["kw"]))
+                      for x in range(g["Wo"])] for y in range(g["Ho"])])
+    np.testing.assert_array_equal(R.tapless_pixels(g), none)
+
+
+def test_tier_table_reaches_every_condition():
+    """What the GPU tests of the tier table run, from the selection rules restated in convtranspose_ref.py (forward_plan:
+    launch_conv_phase and the head of conv_phase_kernel; backward_plan: launch_conv_tap and conv_mfma_wgrad; auto_route: make_plan and
+    resolve_route).  One assertion per condition, so that a row taken out of the table names what it alone provided."""
+    _load()
+    fwd, bwd, routes = {}, {}, {}
+    for name, geom in R.TIER_CASES.items():
+        g = R.normalise(geom)
+        routes[name] = plan(make_desc(g))[1]
+        assert routes[name] == R.auto_route(g), name
+        if g["sh"] * g["sw"] > 1:                                          # the rows on which the phase kernel and the stride > 1 backward run
+            fwd[name], bwd[name] = dict(R.forward_plan(g), g=g), dict(R.backward_plan(g), g=g)
+            assert R.forced_route(g, ROUTE_PHASE) == ROUTE_PHASE and R.forced_route(g, ROUTE_GATHER) == ROUTE_GATHER
+        else:
+            assert R.forced_route(g, ROUTE_PHASE) == routes[name] != ROUTE_PHASE
+
+    def rows(pred, table=fwd):
+        return sorted(n for n, p in table.items() if pred(p))
+
+    def live(p):                                                           # the phases that launch a block that does not return at once
+        return [q for q in p["phases"] if q["pixels"]]
+
+    for wm in (1, 2):
+        assert rows(lambda p: p["wm"] == wm), f"no row runs conv_phase_kernel<{wm}>"
+        for what, pred in (("T = 0", lambda t: t == 0), ("T = 1", lambda t: t == 1), ("even T >= 2", lambda t: t >= 2 and t % 2 == 0),
+                           ("odd T >= 3", lambda t: t >= 3 and t % 2 == 1)):
+            assert rows(lambda p: p["wm"] == wm and any(pred(q["T"]) for q in live(p))), f"no phase with {what} at WM = {wm}"
+        assert rows(lambda p: p["wm"] == wm and p["ctiles"] >= 2 and any(q["T"] == 0 for q in live(p))), \
+            f"no empty phase next to phases of more than one channel tile at WM = {wm}"
+        assert rows(lambda p: p["wm"] == wm and p["ctiles"] % 2 == 1 and p["ctiles"] >= 3 and any(q["taps"] >= 2 for q in live(p))), \
+            f"no row at WM = {wm} whose fetch moves to the next tap in the middle of a pair of k-tiles (odd channel tiles, >= 2 taps)"
+    for n in (1, 2):
+        assert rows(lambda p: p["m_tiles"] == n), f"no row with {n} m-tile(s)"
+    assert rows(lambda p: p["g"]["Cout"] == 64 and any(q["T"] == 0 for q in live(p))), "no empty phase at WM = 1 with a full 64-row tile"
+    assert rows(lambda p: p["wm"] == 2 and p["m_tiles"] == 2 and any(q["T"] == 0 for q in live(p))), "no empty phase at WM = 2 with two m-tiles"
+    for what, pred in (("1", lambda c: c == 1), ("2", lambda c: c == 2), (">= 3", lambda c: c >= 3)):
+        assert rows(lambda p: pred(p["ctiles"])), f"no row with {what} channel tile(s)"
+    for wm in (1, 2):
+        assert rows(lambda p: p["wm"] == wm and any(q["pixels"] == 0 for q in p["phases"])), f"no phase with zero pixels at WM = {wm}"
+    assert rows(lambda p: p["grid_n"] >= 2 and any(0 < q["tiles"] < p["grid_n"] for q in p["phases"])), \
+        "no phase with fewer pixel tiles than the largest phase's >= 2 (the `n0 >= N` return)"
+    assert rows(lambda p: any(q["tiles"] >= 2 and q["spans"] for q in p["phases"])), "no pixel tile that spans two images in a phase of >= 2 tiles"
+    assert rows(lambda p: len({q["N"] for q in live(p)}) >= 3 and any(q["spans"] for q in live(p))), \
+        "no row with pixel tiles that span images in phases of unequal sizes"
+    for wm in (1, 2):
+        assert rows(lambda p: p["wm"] == wm and any(q["tiles"] >= 8 and q["N"] % (256 // wm) for q in p["phases"])), \
+            f"no row with many pixel tiles and a ragged last one at WM = {wm}"
+
+    def strided_subset(p):
+        return 1 < p["rstep"] < p["g"]["sh"] or 1 < p["sstep"] < p["g"]["sw"]
+
+    assert rows(strided_subset), "no row with 1 < rstep < stride"
+    assert rows(lambda p: p["wm"] == 2 and strided_subset(p)), "no row with 1 < rstep < stride at the 128-row tile"
+    assert rows(lambda p: p["wm"] == 2 and p["g"]["dh"] != p["g"]["dw"] and p["g"]["sh"] != p["g"]["sw"]), \
+        "no row with unequal dilations and strides at the 128-row tile"
+    assert rows(lambda p: p["wm"] == 2 and (p["g"]["sh"] > p["g"]["kh"] or p["g"]["sw"] > p["g"]["kw"])), \
+        "no row with stride > kernel at the 128-row tile"
+    for route, word in ((ROUTE_PHASE, "phase"), (ROUTE_GATHER, "gather"), (ROUTE_CONV2D, "conv2d")):
+        assert [n for n, r in routes.items() if r == route], f"`auto` resolves to {word} on no row"
+    assert [n for n, r in routes.items() if r == ROUTE_GATHER and n not in fwd], "no stride-1 row that is not a Conv2d"
+
+    # the backward
+    for wm in (1, 2):
+        assert rows(lambda p: p["dx_wm"] == wm, bwd), f"no row runs dX on conv_tap_kernel<false, {wm}>"
+    for pair in ((1, 32), (1, 64), (1, 128), (1, 256), (2, 32), (2, 64), (2, 128)):
+        assert rows(lambda p: p["wg"] == pair, bwd), f"no row runs conv_wgrad_mfma_kernel<WM, CB> = {pair}"
+    for flag in ("flat", "avec"):
+        for on in (True, False):
+            assert rows(lambda p: p[flag] is on, bwd), f"no row with {flag.upper()} {'on' if on else 'off'}"
+
+
+# ---- ABI edges (no device work: argument checks come first) -------------------------------------------------------------------
 def test_abi_edges():
     _load()
     from neunet_hip._lib import last_error, load_hip_function

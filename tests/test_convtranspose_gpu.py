@@ -6,7 +6,15 @@ step of the reference's DDPM U-Net (tests/golden/ddpm_unet.npz) through examples
 Bounds.  O, dX, dW, db: the project's 1e-4 of max(|ref|, rms(ref)) per element against float64 (assert_close_scaled) and
 rtol = atol = 1e-4 (test_hip_parity.TOL) against the float32 fixture.  At the tile-edge shapes O is also held to the dot-product
 bound 32 * 2^-24 * sum|x||w| + 4 * 2^-24 * |ref| (assert_dot_close's, with the sum taken through the restatement on |X|, |W|),
-and the two routes to twice that of each other.  Each test prints its largest error / bound ratio before it asserts (-s)."""
+and the two routes to twice that of each other.  Each test prints its largest error / bound ratio before it asserts (-s).
+
+The tier table (convtranspose_ref.TIER_CASES; tests/test_convtranspose.py checks on the CPU which template instantiation, k-loop
+length, phase size and weight-gradient configuration each row reaches): O as above on both routes; dX and dW additionally within the
+same dot bound with the sums taken by the restated backward on |X|, |W|, |dO|; db within 4 * 2^-24 * sum|dO| + 2^-24 |ref|.  The
+pixels of a stride phase without a tap hold the bias (or 0) bit for bit; repeated calls, calls with an output left out, `auto`
+against the forced route and a captured graph's replays are bit-identical; operands and outputs that start one float into their
+buffers leave the sentinels around the outputs alone.  None of the bounds is tuned: float32 numpy einsums stand at 0.11 (O), 0.07
+(dX), 0.13 (dW) and 0.18 (db) of them on this table, the kernels at 0.12, 0.08, 0.11 and 0.21 (EXPERIMENTS.md 5.15b)."""
 import ctypes
 import os
 import sys
@@ -45,7 +53,7 @@ def call(name, *args):
 
 
 def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).cuda()
+    return torch.from_numpy(np.array(a, dtype=np.float32, order="C")).cuda()   # a copy: the shared references are read-only
 
 
 def host(t):
@@ -183,6 +191,249 @@ def test_skipped_outputs_leave_the_others_unchanged(hip, golden, name):
                 np.testing.assert_array_equal(host(part[i]), full[i], err_msg=f"output {i} with output {skip} skipped")
     only_db = backward(X, W, dO, g, want=(False, False, True))
     np.testing.assert_array_equal(host(only_db[2]), full[2])
+
+
+# ---- every tier on irregular geometry (convtranspose_ref.TIER_CASES; tests/test_convtranspose.py says what the table reaches) --------
+SETTINGS = dict(ROUTES, auto=0)
+SENTINEL = -7.0
+NULL_ROWS = ("k2s3_w2", "gcd_w2", "bw_w2_cb64")
+GUARD_ROWS = ("k3s2_w2", "uneq_tiles_w2", "nopix_w2", "uneven_w1", "k1s2_w1")
+
+
+def tier_routes(name):
+    """the routes a row is run on: both at stride > 1, else the one resolve_route dictates whatever is asked for"""
+    g = R.normalise(R.TIER_CASES[name])
+    return ["gather", "phase"] if g["sh"] * g["sw"] > 1 else [{R.ROUTE_GATHER: "gather", R.ROUTE_CONV2D: "conv2d"}[R.auto_route(g)]]
+
+
+@pytest.fixture(scope="module")
+def tier_cases():
+    """name -> the seeded float32 inputs, the float64 O / (dX, dW, db) and their bounds: computed once, shared, read-only."""
+    out = {}
+    for name, geom in R.TIER_CASES.items():
+        g, X, W, b, dO = R.make_case(geom, 11)
+        ref = R.forward(X, W, b, g)
+        grads = R.backward(X, W, dO, g)
+        ref0 = R.forward(X, W, None, g)
+        asum = 32 * 2.0 ** -24 * R.abs_sum(X, W, g)                        # R.dot_bound's first term: the same with and without a bias
+        c = dict(g=g, X=X, W=W, b=b, dO=dO, O=ref, bound=asum + 4 * 2.0 ** -24 * np.abs(ref), O0=ref0, bound0=asum + 4 * 2.0 ** -24 * np.abs(ref0),
+                 grads=grads, gbounds=R.backward_bounds(X, W, dO, grads, g))
+        for v in (X, W, b, dO, ref, c["bound"], ref0, c["bound0"]) + tuple(grads) + tuple(c["gbounds"]):
+            v.setflags(write=False)
+        out[name] = c
+    return out
+
+
+def forward_into(setting, X, W, b, O, g):
+    """nnhipConvTranspose2dForward into O with the route switch at `setting`; the previous setting comes back afterwards."""
+    from neunet_hip._lib import load_hip_function
+    d = make_desc(g)
+    prev = load_hip_function("nnhipSetConvTransposeRoute")(SETTINGS[setting])
+    try:
+        call("nnhipConvTranspose2dForward", X, W, b, O, ctypes.byref(d))
+    finally:
+        load_hip_function("nnhipSetConvTransposeRoute")(prev)
+    return O
+
+
+def tier_forward(route, X, W, b, g):
+    """into NaN; a stride-1 row ("conv2d", or "gather" where the layer is no Conv2d) is asked for the phase route and must not follow"""
+    O = torch.full((g["B"], g["Cout"], g["Ho"], g["Wo"]), NAN, device="cuda")
+    forward_into("phase" if g["sh"] * g["sw"] == 1 else route, X, W, b, O, g)
+    torch.cuda.synchronize()
+    return host(O)
+
+
+def ratio(got, ref, bound):
+    return float(np.max(np.abs(np.asarray(got, np.float64) - ref) / np.maximum(bound, 1e-300))) if np.size(ref) else 0.0
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def check_forward(tag, O, c, bias=True):
+    ref, bound = (c["O"], c["bound"]) if bias else (c["O0"], c["bound0"])   # O0: the float64 sum without the bias (= O - b)
+    scale = 1e-4 * np.maximum(np.abs(ref), np.sqrt(np.mean(ref ** 2))) + 1e-30
+    print(f"{tag}: max |err| / dot bound = {ratio(O, ref, bound):.3f}, / (1e-4 scale) = {ratio(O, ref, scale):.3f}")
+    assert not np.isnan(O).any(), f"{tag}: output pixels left unwritten"
+    assert_within(O, ref, bound, f"{tag} vs float64 (dot bound)")
+    assert_close_scaled(O, ref, tol=1e-4, err_msg=f"{tag} vs float64")
+    # the pixels of the phases without a tap hold the bias (or zero) itself, not a sum that rounds to it
+    mask = R.tapless_pixels(c["g"])
+    want = np.broadcast_to((c["b"] if bias else np.zeros_like(c["b"])).reshape(1, -1, 1), O[:, :, mask].shape)
+    np.testing.assert_array_equal(bits(O[:, :, mask] + 0.0), bits(want), err_msg=f"{tag}: bias-only pixels")
+
+
+def check_backward(tag, got, c):
+    worst = {}
+    for k, o, r, bd in zip(("dX", "dW", "db"), got, c["grads"], c["gbounds"]):
+        if o is None:
+            continue
+        scale = 1e-4 * np.maximum(np.abs(r), np.sqrt(np.mean(r ** 2))) + 1e-30
+        worst[k] = ratio(o, r, bd)
+        print(f"{tag} {k}: max |err| / {'sum' if k == 'db' else 'dot'} bound = {worst[k]:.3f}, / (1e-4 scale) = {ratio(o, r, scale):.3f}")
+    for k, o, r, bd in zip(("dX", "dW", "db"), got, c["grads"], c["gbounds"]):
+        if o is None:
+            continue
+        assert not np.isnan(o).any(), f"{tag} {k} not fully written"
+        assert_close_scaled(o, r, tol=1e-4, err_msg=f"{tag} {k} vs float64")
+        assert_within(o, r, bd, f"{tag} {k} vs float64 ({'sum' if k == 'db' else 'dot'} bound)")
+    return worst
+
+
+@pytest.mark.parametrize("name,route", [(n, r) for n in R.TIER_CASES for r in tier_routes(n)])
+def test_tier_forward(hip, tier_cases, name, route):
+    c = tier_cases[name]
+    g = c["g"]
+    Xd, Wd, bd = dev(c["X"]), dev(c["W"]), dev(c["b"])
+    O = tier_forward(route, Xd, Wd, bd, g)
+    check_forward(f"{name} {route} O", O, c)
+    np.testing.assert_array_equal(bits(O), bits(tier_forward(route, Xd, Wd, bd, g)), err_msg=f"{route}: two runs differ")
+    check_forward(f"{name} {route} O, no bias", tier_forward(route, Xd, Wd, None, g), c, bias=False)
+    if g["sh"] * g["sw"] > 1:
+        other = tier_forward("gather" if route == "phase" else "phase", Xd, Wd, bd, g)
+        print(f"{name} {route} vs the other route: max |diff| / (2 dot bound) = {ratio(O, other.astype(np.float64), 2 * c['bound']):.3f}")
+        assert_within(O, other, 2 * c["bound"], "phase vs gather")
+
+
+@pytest.mark.parametrize("name", list(R.TIER_CASES))
+def test_tier_backward(hip, tier_cases, name):
+    c = tier_cases[name]
+    g = c["g"]
+    Xd, Wd, dOd = dev(c["X"]), dev(c["W"]), dev(c["dO"])
+    full = [host(t) for t in backward(Xd, Wd, dOd, g)]
+    check_backward(name, full, c)
+    for k, a, b_ in zip(("dX", "dW", "db"), full, backward(Xd, Wd, dOd, g)):
+        np.testing.assert_array_equal(bits(a), bits(host(b_)), err_msg=f"{k}: two runs differ")
+    if name in NULL_ROWS:
+        for skip in range(3):
+            part = backward(Xd, Wd, dOd, g, want=tuple(i != skip for i in range(3)))
+            assert part[skip] is None
+            for i in range(3):
+                if i != skip:
+                    np.testing.assert_array_equal(bits(host(part[i])), bits(full[i]), err_msg=f"output {i} with output {skip} skipped")
+
+
+class Fenced:
+    """A tensor that starts one float into a larger buffer -- 4-byte but not 16-byte aligned -- with 65 floats of SENTINEL before it and
+    64 after it (torch's allocations are 512-byte aligned); with `data`: an operand, one float in, nothing behind it."""
+
+    def __init__(self, shape, fill=NAN, data=None):
+        n = int(np.prod(shape))
+        self.lo = 1 if data is not None else 65
+        self.buf = torch.full((self.lo + n + (0 if data is not None else 64),), SENTINEL, device="cuda")
+        self.view = self.buf[self.lo:self.lo + n].view(*shape)
+        assert self.view.data_ptr() % 16 == 4 and self.buf.data_ptr() % 16 == 0
+        if data is not None:
+            self.view.copy_(dev(data))
+        else:
+            self.view.fill_(fill)
+
+    def intact(self):
+        b = host(self.buf)
+        n = self.view.numel()
+        return bool((bits(b[:self.lo]) == bits(np.float32(SENTINEL))).all() and (bits(b[self.lo + n:]) == bits(np.float32(SENTINEL))).all())
+
+
+@pytest.mark.parametrize("name", GUARD_ROWS)
+def test_guard_bands_and_unaligned_operands(hip, tier_cases, name):
+    """Every operand and output one float into its buffer (no float4 store in conv_tap_kernel, no 16-byte dO load in the weight
+    gradient), the outputs between sentinels that must keep their bits: a store the kernel should have skipped, or one past a
+    tensor's end, lands on them."""
+    c = tier_cases[name]
+    g = c["g"]
+    X, W, b, dO = (Fenced(c[k].shape, data=c[k]) for k in ("X", "W", "b", "dO"))
+    for route in tier_routes(name):
+        O = Fenced((g["B"], g["Cout"], g["Ho"], g["Wo"]))
+        forward_into(route, X.view, W.view, b.view, O.view, g)
+        torch.cuda.synchronize()
+        check_forward(f"{name} {route} O, one float in", host(O.view), c)
+        assert O.intact(), f"{route}: wrote outside O"
+    outs = [Fenced(s) for s in (c["X"].shape, c["W"].shape, c["b"].shape)]
+    call("nnhipConvTranspose2dBackward", X.view, W.view, dO.view, outs[0].view, outs[1].view, outs[2].view, ctypes.byref(make_desc(g)))
+    torch.cuda.synchronize()
+    check_backward(f"{name}, one float in,", [host(o.view) for o in outs], c)
+    for k, o in zip(("dX", "dW", "db"), outs):
+        assert o.intact(), f"wrote outside {k}"
+    assert all(t.intact() for t in (X, W, b, dO))
+
+
+@pytest.mark.parametrize("name", ["k3s2_w2", "k2s3_w2", "s1_bigpad_w2", "s1_conv_w2"])
+def test_route_auto_matches_the_forced_route(hip, tier_cases, name):
+    """`auto` = the route the restated resolve_route names, bit for bit: phase, gather (empty phases), gather (stride 1), conv2d."""
+    from neunet_hip._lib import load_hip_function
+    c = tier_cases[name]
+    g = c["g"]
+    Xd, Wd, bd = dev(c["X"]), dev(c["W"]), dev(c["b"])
+    resolved = {R.ROUTE_PHASE: "phase", R.ROUTE_GATHER: "gather", R.ROUTE_CONV2D: "conv2d"}[R.auto_route(g)]
+    outs = {}
+    before = load_hip_function("nnhipGetConvTransposeRoute")()
+    try:
+        for setting in ("auto", "phase", "gather"):
+            O = torch.full((g["B"], g["Cout"], g["Ho"], g["Wo"]), NAN, device="cuda")
+            outs[setting] = host(forward_into(setting, Xd, Wd, bd, O, g))
+    finally:
+        load_hip_function("nnhipSetConvTransposeRoute")(before)
+    assert load_hip_function("nnhipGetConvTransposeRoute")() == before
+    print(f"{name}: auto -> {resolved}")
+    if resolved == "conv2d":
+        O = torch.full((g["B"], g["Cout"], g["Ho"], g["Wo"]), NAN, device="cuda")
+        eh, ew = g["dh"] * (g["kh"] - 1), g["dw"] * (g["kw"] - 1)
+        from neunet_hip._lib import Conv2dDesc
+        cd = Conv2dDesc(g["B"], g["Cin"], g["H"], g["W"], g["Cout"], g["kh"], g["kw"], 1, 1, g["dh"], g["dw"],
+                        eh - g["pu"], eh - g["pd"] + g["oph"], ew - g["pl"], ew - g["pr"] + g["opw"])
+        call("nnhipConv2dForward", Xd, Wd, bd, O, ctypes.byref(cd))
+        outs["conv2d"] = host(O)
+    np.testing.assert_array_equal(bits(outs["auto"]), bits(outs[resolved]))
+    if g["sh"] * g["sw"] == 1:                                            # nothing to force at stride 1
+        np.testing.assert_array_equal(bits(outs["phase"]), bits(outs["auto"]))
+        np.testing.assert_array_equal(bits(outs["gather"]), bits(outs["auto"]))
+    check_forward(f"{name} auto O", outs["auto"], c)
+
+
+@pytest.mark.parametrize("name", ["k3s2_w1", "k3s2_c3_w2"])
+def test_phase_forward_in_a_captured_graph(hip, tier_cases, name):
+    """One forward on the phase route (weight repack + conv_phase_kernel) captured on one stream after an eager call has sized the
+    workspace and set the kernel's shared-memory attribute; two replays into NaN equal the eager bits."""
+    from neunet_hip._lib import load_hip_function
+    c = tier_cases[name]
+    g = c["g"]
+    assert R.forward_plan(g)["wm"] == (2 if name.endswith("w2") else 1)
+    Xd, Wd, bd = dev(c["X"]), dev(c["W"]), dev(c["b"])
+    eager = tier_forward("phase", Xd, Wd, bd, g)
+    check_forward(f"{name} phase O, eager", eager, c)
+    O = torch.full((g["B"], g["Cout"], g["Ho"], g["Wo"]), NAN, device="cuda")
+    d = make_desc(g)
+    torch.cuda.synchronize()
+    prev = load_hip_function("nnhipSetConvTransposeRoute")(ROUTES["phase"])
+    try:
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            call("nnhipConvTranspose2dForward", Xd, Wd, bd, O, ctypes.byref(d))
+    finally:
+        load_hip_function("nnhipSetConvTransposeRoute")(prev)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(O).all()), "capturing runs nothing"
+    for replay in range(2):
+        O.fill_(NAN)
+        graph.replay()
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bits(host(O)), bits(eager), err_msg=f"replay {replay}")
+    del graph
+
+
+def test_tier_batch_zero_touches_nothing(hip, tier_cases):
+    c = tier_cases["k3s2_w2"]
+    g = dict(c["g"], B=0)
+    Xd, Wd, bd, dOd = dev(c["X"]), dev(c["W"]), dev(c["b"]), dev(c["dO"])
+    outs = [Fenced(s) for s in (c["O"].shape, c["X"].shape, c["W"].shape, c["b"].shape)]
+    for route in ("phase", "gather"):
+        forward_into(route, Xd, Wd, bd, outs[0].view, g)
+    call("nnhipConvTranspose2dBackward", Xd, Wd, dOd, outs[1].view, outs[2].view, outs[3].view, ctypes.byref(make_desc(g)))
+    torch.cuda.synchronize()
+    for o in outs:
+        assert o.intact() and bool(torch.isnan(o.view).all())
 
 
 # ---- U-Net glue ---------------------------------------------------------------------------------------------------------------
