@@ -294,6 +294,13 @@ extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, floa
     FusedOptimizer* fo = static_cast<FusedOptimizer*>(opt);
     hipStream_t st = (hipStream_t)s;
     const int n = n_tensors;
+    float* dstate = nullptr;
+    if (step == 0) {  // device-driven step counter (set with nnhipFusedOptimizerSetStep): graph-replay safe.  Checked with the
+                      // other arguments, before the plan below makes the first device call
+        NNHIP_CHECK_ARG(fo->dev_state != nullptr && fo->hyper_set, NNHIP_EINVAL,
+                        "nnhipFusedAdamWMultiTensorStep: step == 0 needs nnhipFusedOptimizerSetStep and SetHyper first");
+        dstate = fo->dev_state;
+    }
     const void* const* const tables[4] = {reinterpret_cast<const void* const*>(p), reinterpret_cast<const void* const*>(g),
                                           reinterpret_cast<const void* const*>(m), reinterpret_cast<const void* const*>(v)};
     const unsigned char* dev_blob = nullptr;
@@ -302,12 +309,6 @@ extern "C" int nnhipFusedAdamWMultiTensorStep(void* opt, int32_t n_tensors, floa
     if (nblk == 0) return 0;
 
     const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, step > 0 ? step : 1, decay_mode, grad_scale);
-    float* dstate = nullptr;
-    if (step == 0) {  // device-driven step counter (set with nnhipFusedOptimizerSetStep): graph-replay safe
-        NNHIP_CHECK_ARG(fo->dev_state != nullptr && fo->hyper_set, NNHIP_EINVAL,
-                        "nnhipFusedAdamWMultiTensorStep: step == 0 needs nnhipFusedOptimizerSetStep and SetHyper first");
-        dstate = fo->dev_state;
-    }
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nblk), dim3(256), 0, st, dev_blob, n, nblk, h, dstate, beta1,
                        beta2, chunk, fo->grad_div);
     NNHIP_LAUNCH_CHECK("adamw_multi_kernel");

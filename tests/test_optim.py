@@ -146,6 +146,28 @@ def test_multi_tensor_argument_errors(lib):
         load_hip_function("nnhipDestroyFusedOptimizer")(opt)
 
 
+def test_adam_device_stepping_needs_a_prepared_handle(lib):
+    """nnhipFusedAdamWMultiTensorStep with step == 0 (device-side stepping) on a handle that never saw nnhipFusedOptimizerSetStep /
+    SetHyper: the documented error, raised with the other argument checks -- before the plan is built and uploaded, so no device call
+    precedes it and the pointers are never dereferenced."""
+    from ctypes import POINTER, c_int64, c_void_p, cast
+    from neunet_hip._lib import NeunetHipError, call_hip_function, load_hip_function
+    opt = load_hip_function("nnhipCreateFusedOptimizer")()
+    assert opt
+    tab = cast((c_void_p * 2)(0x1000, 0x1000), POINTER(c_void_p))
+    sizes = cast((c_int64 * 2)(16, 5), POINTER(c_int64))
+    try:
+        for mode in (0, 1):
+            with pytest.raises(NeunetHipError, match="step == 0 needs nnhipFusedOptimizerSetStep and SetHyper first"):
+                call_hip_function("nnhipFusedAdamWMultiTensorStep", opt, 2, tab, tab, tab, tab, sizes, 0.01, 0.9, 0.999, 1e-8, 0.01, 0,
+                                  mode, 1.0, None)
+        with pytest.raises(NeunetHipError, match="bad n_tensors/step"):
+            call_hip_function("nnhipFusedAdamWMultiTensorStep", opt, 2, tab, tab, tab, tab, sizes, 0.01, 0.9, 0.999, 1e-8, 0.01, -1, 0, 1.0,
+                              None)
+    finally:
+        load_hip_function("nnhipDestroyFusedOptimizer")(opt)
+
+
 # The reference's constructors (neunet/optim.py:76-244): parameter names and defaults, in order.
 REFERENCE_SIGNATURES = {
     "SGD": [("params", inspect.Parameter.empty), ("lr", 0.01)],
