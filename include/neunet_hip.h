@@ -383,7 +383,8 @@ int nnhipCrossEntropyLoss(float* logits, float* dlogits_or_null, float* loss_row
  *   count_out (NULL-able): #{labels != ignore_index} for 'm'.
  * The 'mean' denominator is derived from the labels inside the launch (no count launch, no host sync); the per-block
  * loss sums meet in the last block to finish (arrival ticket).  A label outside [0, n_cols) that is not ignore_index
- * gives zero loss and zero gradient.  Rows of any width (looped above 16384 columns). */
+ * gives zero loss and zero gradient.  'mean' with no live row at all (every label ignored or out of range): loss 0 and a zero
+ * gradient, as nnhipNLLLossForwardBackward, not NumPy's 0 / 0.  Rows of any width (looped above 16384 columns). */
 int nnhipCrossEntropyLossEx(float* logits, float* dlogits_or_null, float* loss_rows, float* lse, const void* labels,
                             int32_t label_bytes, const float* class_weight_or_null, int64_t logits_stride,
                             int64_t ignore_index, int64_t n_rows, int64_t n_cols, char reduction,

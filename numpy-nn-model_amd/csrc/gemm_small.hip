@@ -164,7 +164,9 @@ __device__ __forceinline__ void sg_tile16_dz(const SmallMlpBwd& q, int bx, int b
         float sacc = 0.f;
 #pragma unroll
         for (int c = 0; c < SG_MLP_MAXC; ++c) sacc = fmaf(dOs[b * 16 + c], w2s[c * 16 + oo], sacc);
-        dZs[b * 17 + oo] = hval > 0.f ? sacc : 0.f;
+        // the reference's mask is a PRODUCT (activations.py:44-45, grad * (f_x > 0)): an infinite or NaN gradient under a closed
+        // mask is NaN there, not 0 -- an overflowed step must not leave finite weights behind where the reference leaves none
+        dZs[b * 17 + oo] = hval > 0.f ? sacc : sacc * 0.f;
     };
 #pragma unroll
     for (int e = 0; e < PRE; ++e) {

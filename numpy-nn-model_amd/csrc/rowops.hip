@@ -1033,6 +1033,14 @@ __device__ __forceinline__ void ce_prologue(const CeArgs& a, float* red, int* ir
     }
 }
 
+// The 'mean' loss from the sum of the row losses.  Where the launch derived the denominator from the labels and found no live row
+// (every label ignored or out of range) the loss is 0, next to the zero gradient `scale` gives there (ce_prologue) and as
+// nnhipNLLLossForwardBackward answers the same labels -- not the 0 / 0 = NaN of the reference's NumPy expression.  A denominator
+// the CALLER supplied (count_dev, scale_host) is divided by as it is.
+__device__ __forceinline__ float ce_mean(const CeArgs& a, float s, float denom) {
+    return (a.count_in_kernel || a.denom_dev) && !(denom > 0.f) ? 0.f : s / denom;
+}
+
 // Publish this block's loss sum, and let the last arrival reduce all of them.  `lsum` is valid on thread 0.
 template <int BS>
 __device__ __forceinline__ void ce_epilogue(const CeArgs& a, float lsum, float denom, float* red, int* ired) {
@@ -1049,7 +1057,7 @@ __device__ __forceinline__ void ce_epilogue(const CeArgs& a, float lsum, float d
             if (old >> 63) {
                 const float other = __uint_as_float((unsigned)(old & 0xffffffffull));
                 const float s = ((old >> 32) & 1ull) == 0 ? other + lsum : lsum + other;
-                a.loss_out[0] = a.mode == 1 ? s / denom : s;
+                a.loss_out[0] = a.mode == 1 ? ce_mean(a, s, denom) : s;
                 __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -1076,7 +1084,7 @@ __device__ __forceinline__ void ce_epilogue(const CeArgs& a, float lsum, float d
     }
     s = block_sum<BS / 64>(s, red);
     if (threadIdx.x == 0) {
-        a.loss_out[0] = a.mode == 1 ? s / denom : s;
+        a.loss_out[0] = a.mode == 1 ? ce_mean(a, s, denom) : s;
         __hip_atomic_store(&a.sync[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -1334,7 +1342,7 @@ __global__ __launch_bounds__(1024) void ce_small_kernel(const CeArgs a) {
     if (threadIdx.x == 0) {
         float t = 0.f;
         for (int i = 0; i < 16; ++i) t += red[i];
-        a.loss_out[0] = a.mode == 1 ? t / denom : t;
+        a.loss_out[0] = a.mode == 1 ? ce_mean(a, t, denom) : t;
     }
 }
 
