@@ -196,7 +196,10 @@ extern "C" int nnhipOptimizerRuleMultiTensorStep(void* opt, int32_t rule, int32_
     NNHIP_CHECK_ARG((ns < 1 || s1) && (ns < 2 || s2), NNHIP_EINVAL, "nnhipOptimizerRuleMultiTensorStep: null state table (the rule has %d state stream(s))", ns);
     float* dstate = nullptr;
     const float* grad_div = nullptr;
-    if (int rc = fused_optimizer_state(opt, step, &dstate, &grad_div)) return rc;      // step == 0 without SetStep + SetHyper: EINVAL
+    if (int rc = fused_optimizer_state(opt, step, &dstate, &grad_div)) {               // step == 0 without SetStep + SetHyper: EINVAL,
+        set_last_error("nnhipOptimizerRuleMultiTensorStep: step == 0 needs nnhipFusedOptimizerSetStep and SetHyper first");   // before the plan
+        return rc;
+    }
     hipStream_t st = (hipStream_t)s;
     const void* const* const tables[4] = {reinterpret_cast<const void* const*>(p), reinterpret_cast<const void* const*>(g),
                                           reinterpret_cast<const void* const*>(s1), reinterpret_cast<const void* const*>(s2)};
