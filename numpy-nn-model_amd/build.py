@@ -19,7 +19,7 @@ OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
 SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip", "tensor_ops.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"), os.path.join(CSRC, "ew_map.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"), os.path.join(CSRC, "ew_map.h"), os.path.join(CSRC, "deferred_queue.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
 

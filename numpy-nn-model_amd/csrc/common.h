@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <mutex>
+
 #include "../../include/neunet_hip.h"
 
 namespace nnhip {
@@ -40,13 +42,12 @@ void* workspace(size_t bytes);
 void* workspace_arena(int which, size_t bytes);   // 0 = the general block (== workspace), 1 = the grouped dW launch's slabs,
                                                   // 2 = scratch of entries that call block-0 users while it is live: the LSTM entries' packed weights and dG, ConvTranspose2d's dW
 bool workspace_locked();               // nnhipWorkspaceLock(1): a captured hipGraph holds library-owned addresses -- nothing may move
-// Deferred parameter gradients (nnhipWeightGradDefer, linear.hip): on while Tensor.backward() walks the tape.  conv2d.hip queues the
-// REDUCE of a small-channel conv's per-image partial weight gradients behind it (the partials sit in an arena of their own, not
-// in the shared workspace) and launches the queued reduces as one grid at the flush.
+// Deferred parameter gradients (nnhipWeightGradDefer, linear.hip): on while Tensor.backward() walks the tape.  conv2d.hip and rowops.hip
+// then queue the REDUCE of a small-channel conv's weight-gradient partials / a norm's dw, db column sums (deferred_queue.h).
 bool wgrad_defer_on();
-int conv_reduce_flush(void* stream);
+int conv_reduce_flush(void* stream);   // the queued reduces as one launch
 void conv_reduce_cleanup();            // frees the partials arena (nnhipCleanup)
-int colsum_flush(void* stream);        // rowops.hip: the queued RMSNorm dw / db column sums of a backward pass, as one launch
+int colsum_flush(void* stream);
 void colsum_cleanup();
 // one deferred parameter-gradient GEMM (gemm.hip: gemm_f32_wgrad_group): C[M,N] = A^T B with A [K, M] and B [K, N] dense
 struct WgradJob {
@@ -57,8 +58,8 @@ struct WgradJob {
 // 256 bytes of device zeros, allocated once per process (never freed): where out-of-range GEMM lanes load from.
 const float* zero_block();
 // Library-owned, zero-initialised device words for in-launch arrival tickets (kSyncWords unsigned ints, never freed).
-// Every kernel that uses a slot leaves it zeroed for the next launch.  Slots are per kernel family (the library's
-// workspace already makes it one-stream-at-a-time per process).
+// Every kernel that uses a slot leaves it zeroed for the next launch.  Slots are per kernel family; g_shared_state_guard
+// (below) keeps their users to one stream at a time.
 constexpr int kSyncWords = 1024;
 enum SyncSlot { SYNC_CE = 0, SYNC_MLP = 24 };
 unsigned* sync_words();
@@ -69,16 +70,40 @@ unsigned* sync_words();
 enum DeviceErrorCode { NNHIP_DEVERR_NONE = 0, NNHIP_DEVERR_MLP_BARRIER = 1, NNHIP_DEVERR_LSTM_SHAPE = 2, NNHIP_DEVERR_KVCACHE_FULL = 3, NNHIP_DEVERR_RECURRENT_SHAPE = 4 };
 unsigned* device_error_word();                   // device-side address
 int device_error_status(const char* who);        // 0, or NNHIP_EDEVICE with the message set
-// Order this launch behind the previous user of the sync words / ticket partials when it arrives on another stream (runtime.hip).
-int serialize_shared_state(hipStream_t st);
-void shared_state_done(hipStream_t st);        // the user's launches are enqueued: leave an event for the next stream to wait on
-struct SharedStateUse {                         // RAII: construct after serialize_shared_state(), every return path reports the launches
-    hipStream_t st;
-    explicit SharedStateUse(hipStream_t s) : st(s) {}
-    ~SharedStateUse() { shared_state_done(st); }
-    SharedStateUse(const SharedStateUse&) = delete;
-    SharedStateUse& operator=(const SharedStateUse&) = delete;
+// Stream ordering of library-owned scratch that exists once per process (runtime.hip has the reasoning).  One StreamGuard per piece:
+// acquire(st) before the first launch that touches the scratch; the launches are reported when the returned Use ends.  A Use comes
+// only from acquire, so nothing is released that was not acquired.  An empty Use: `st` could not be ordered, `rc` says why.
+bool stream_capturing(hipStream_t st);
+class StreamGuard {
+public:
+    class Use {
+    public:
+        Use() = default;
+        Use(Use&& o) noexcept { *this = static_cast<Use&&>(o); }
+        Use& operator=(Use&& o) noexcept { done(callers_); g_ = o.g_; st_ = o.st_; callers_ = o.callers_; rc = o.rc; o.g_ = nullptr; return *this; }
+        ~Use() { done(callers_); }
+        explicit operator bool() const { return g_ != nullptr; }
+        // The launches are enqueued.  st_is_callers = false: by now the stream is a handle kept from an earlier call -- no event is
+        // recorded on it, and the next stream synchronises with the device instead.
+        void done(bool st_is_callers) { if (g_) g_->release(st_, st_is_callers); g_ = nullptr; }
+        int rc = 0;
+    private:
+        friend class StreamGuard;
+        StreamGuard* g_ = nullptr;
+        hipStream_t st_ = nullptr;               // the stream of acquire(); callers_: its st_is_callers
+        bool callers_ = true;
+    };
+    Use acquire(hipStream_t st, bool st_is_callers = true);
+    void reset();                                // nnhipCleanup: destroys the event
+private:
+    void release(hipStream_t st, bool record);
+    std::mutex mu_;
+    hipStream_t last_ = nullptr;                 // the previous user's stream: compared, never passed to the runtime
+    bool have_last_ = false, ev_live_ = false;
+    hipEvent_t ev_ = nullptr;                    // recorded behind the previous user's launches
 };
+extern StreamGuard g_shared_state_guard;         // the sync words and the ticket partials behind them
+extern StreamGuard g_wgrad_slab_guard;           // workspace block 1: the slabs of the grouped dW launch (gemm.hip)
 
 // ---- device helpers ----------------------------------------------------------------------------
 // Wave64 all-reduce on the DPP lanes, no LDS traffic and no address registers: four row-local steps (quad_perm xor 1,

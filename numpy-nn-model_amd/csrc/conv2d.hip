@@ -12,9 +12,8 @@
 // At the C5 shapes (K = 9/72, Cout = 8/16) the work is HBM/latency bound, not MFMA bound.
 #include <stdlib.h>
 
-#include <mutex>
-
 #include "conv_common.h"
+#include "deferred_queue.h"
 
 namespace nnhip {
 
@@ -82,113 +81,32 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_group_kernel(const Conv
     }
 }
 
-static std::mutex g_crq_mu;
-static ConvReduceJob g_crq[CRQ_MAX];
-static int g_crq_n = 0;
-static hipStream_t g_crq_st = nullptr;
-static float* g_crq_arena = nullptr;
-static size_t g_crq_cap = 0, g_crq_used = 0;              // floats
-// The arena is reused from offset 0 after every flush, and the flushed reduce reads it on the stream it was launched on.  A job on
-// ANOTHER stream must not write its partials before that reduce is done: g_crq_reader is the stream of the last flushed reduce,
-// g_crq_writer the stream that has been ordered behind it (or is it).  Each new reader was itself ordered behind the one before.
-static hipStream_t g_crq_reader = nullptr, g_crq_writer = nullptr;
-static bool g_crq_read = false;                           // a reduce has been launched on g_crq_reader
-static hipEvent_t g_crq_ev = nullptr;
-
-static int crq_flush_locked(hipStream_t st) {
-    if (g_crq_n == 0) return 0;
+static int conv_reduce_group_launch(const ConvReduceJob* q, int n, int, hipStream_t st) {
     ConvReduceGroup grp;
-    int blocks = 0;
-    for (int i = 0; i < CRQ_MAX; ++i) {
-        grp.start[i] = blocks;
-        if (i < g_crq_n) { grp.j[i] = g_crq[i]; blocks += (int)ceil_div((int64_t)g_crq[i].Cout * g_crq[i].ncols, 4); }
-        else grp.j[i] = g_crq[0];
-    }
-    grp.start[CRQ_MAX] = blocks;
-    for (int i = g_crq_n; i < CRQ_MAX; ++i) grp.start[i] = blocks;      // no block maps to an unused slot
-    const int n = g_crq_n;
-    g_crq_n = 0;
-    g_crq_used = 0;
-    g_crq_reader = g_crq_writer = st;
-    g_crq_read = true;
+    const int blocks = group_starts<CRQ_MAX>(q, n, grp.j, grp.start, [](const ConvReduceJob& j) { return (int)ceil_div((int64_t)j.Cout * j.ncols, 4); });
     if (n == 1)
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grp.j[0].part, grp.j[0].dW, grp.j[0].db,
-                           grp.j[0].chunks, grp.j[0].Cout, grp.j[0].Nw, grp.j[0].ncols);
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q[0].part, q[0].dW, q[0].db, q[0].chunks,
+                           q[0].Cout, q[0].Nw, q[0].ncols);
     else
         hipLaunchKernelGGL(conv_wgrad_reduce_group_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grp);
     NNHIP_LAUNCH_CHECK("conv_wgrad_reduce_group_kernel");
     return 0;
 }
-int conv_reduce_flush(void* stream) {
-    std::lock_guard<std::mutex> lk(g_crq_mu);
-    return crq_flush_locked(g_crq_n ? g_crq_st : (hipStream_t)stream);
-}
-void conv_reduce_cleanup() {
-    std::lock_guard<std::mutex> lk(g_crq_mu);
-    g_crq_n = 0;
-    g_crq_used = g_crq_cap = 0;
-    if (g_crq_arena) (void)hipFree(g_crq_arena);
-    g_crq_arena = nullptr;
-    if (g_crq_ev) (void)hipEventDestroy(g_crq_ev);
-    g_crq_ev = nullptr;
-    g_crq_read = false;
-}
-// Orders `st` behind the last flushed reduce (see g_crq_reader) before `st` may write the arena.  While `st` is being captured
-// nothing runs and nothing may be waited for (a wait or a query outside the graph would invalidate the capture): the launch is only
-// recorded, and whoever replays the graph orders the replay.  Otherwise an event; if the reader is itself being captured the arena is
-// not handed out (false: the caller takes the shared workspace and reduces at once).
-static bool crq_order_writer(hipStream_t st) {
-    if (!g_crq_read || st == g_crq_reader || st == g_crq_writer) return true;
-    hipStreamCaptureStatus cw = hipStreamCaptureStatusNone, cr = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cw);
-    if (cw != hipStreamCaptureStatusNone) return true;
-    if (g_crq_reader != nullptr) (void)hipStreamIsCapturing(g_crq_reader, &cr);   // (the null stream cannot be captured)
-    if (cr != hipStreamCaptureStatusNone) return false;
-    if (!g_crq_ev && hipEventCreateWithFlags(&g_crq_ev, hipEventDisableTiming) != hipSuccess) g_crq_ev = nullptr;
-    bool ok = g_crq_ev && hipEventRecord(g_crq_ev, g_crq_reader) == hipSuccess && hipStreamWaitEvent(st, g_crq_ev, 0) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        ok = hipStreamSynchronize(g_crq_reader) == hipSuccess;
-    }
-    if (ok) g_crq_writer = st;
-    return ok;
-}
+static DeferredQueue<ConvReduceJob, CRQ_MAX> g_crq(conv_reduce_group_launch);
+int conv_reduce_flush(void* stream) { return g_crq.flush((hipStream_t)stream); }
+void conv_reduce_cleanup() { g_crq.cleanup(); }
 // Where a weight-gradient kernel writes its `floats` partials: the arena when its reduce can wait for the flush (*deferred),
 // else the shared workspace (reduce launched at once).  nullptr: out of memory.
 static float* conv_partials(size_t floats, hipStream_t st, bool* deferred, int* rc) {
     static const bool on = []() { const char* e = getenv("NNHIP_CONV_DEFER_REDUCE"); return !e || atoi(e) != 0; }();
-    *deferred = false;
     *rc = 0;
-    if (on && wgrad_defer_on()) {
-        std::lock_guard<std::mutex> lk(g_crq_mu);
-        if (g_crq_n && (g_crq_st != st || g_crq_n == CRQ_MAX || g_crq_used + floats > g_crq_cap)) *rc = crq_flush_locked(g_crq_st);
-        if (floats > g_crq_cap && !workspace_locked()) {      // grow (nothing is queued here); never while a captured graph holds the address
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(st, &cs);
-            if (cs == hipStreamCaptureStatusNone) {
-                if (g_crq_arena) (void)hipFree(g_crq_arena);  // (synchronises: earlier reduces are done with it)
-                g_crq_arena = nullptr;
-                g_crq_cap = 0;
-                g_crq_read = false;
-                const size_t want = floats + (floats >> 1);
-                if (hipMalloc(&g_crq_arena, want * sizeof(float)) == hipSuccess) g_crq_cap = want;
-                else g_crq_arena = nullptr;
-            }
-        }
-        if (floats <= g_crq_cap - g_crq_used && crq_order_writer(st)) {
-            float* p = g_crq_arena + g_crq_used;
-            g_crq_used += (floats + 63) & ~(size_t)63;
-            g_crq_st = st;
-            *deferred = true;
-            return p;
-        }
-    }
-    return static_cast<float*>(workspace(floats * sizeof(float)));
+    float* p = on && wgrad_defer_on() ? g_crq.reserve(floats, 1, 0, st, floats + (floats >> 1), rc) : nullptr;
+    *deferred = p != nullptr;
+    return p || *rc ? p : static_cast<float*>(workspace(floats * sizeof(float)));
 }
 static int conv_reduce(const float* part, float* dW, float* db, int chunks, int Cout, int Nw, int ncols, hipStream_t st, bool deferred) {
     if (deferred) {
-        std::lock_guard<std::mutex> lk(g_crq_mu);
-        g_crq[g_crq_n++] = ConvReduceJob{part, dW, db, chunks, Cout, Nw, ncols};
+        g_crq.push(ConvReduceJob{part, dW, db, chunks, Cout, Nw, ncols});
         return 0;
     }
     hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)ceil_div((int64_t)Cout * ncols, 4)), dim3(256), 0, st, part, dW, db, chunks,

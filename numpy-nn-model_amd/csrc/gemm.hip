@@ -846,13 +846,16 @@ bool gemm_f32_wgrad_group_ok(const WgradJob& j) {
     return tiles <= 256;                                    // a GEMM that fills the chip on its own gains nothing from company
 }
 
-int gemm_f32_wgrad_group(const WgradJob* jobs, int n, hipStream_t st) {
+// st_is_callers = false: `st` is the queue's stream kept from an earlier call (a flush forced by a stream change)
+int gemm_f32_wgrad_group(const WgradJob* jobs, int n, hipStream_t st, bool st_is_callers) {
     if (n <= 0) return 0;
     if (n > GEMM_GROUP_MAX) {
         for (int i = 0; i < n; i += GEMM_GROUP_MAX)
-            if (int rc = gemm_f32_wgrad_group(jobs + i, n - i < GEMM_GROUP_MAX ? n - i : GEMM_GROUP_MAX, st)) return rc;
+            if (int rc = gemm_f32_wgrad_group(jobs + i, n - i < GEMM_GROUP_MAX ? n - i : GEMM_GROUP_MAX, st, st_is_callers)) return rc;
         return 0;
     }
+    const StreamGuard::Use in_use = g_wgrad_slab_guard.acquire(st, st_is_callers);     // the slabs are one block per process
+    if (!in_use) return in_use.rc;
     GemmGroup g{};
     ReduceGroup rg{};
     size_t floats = 0;

@@ -8,7 +8,7 @@
 
 namespace nnhip {
 bool gemm_f32_wgrad_group_ok(const WgradJob& j);
-int gemm_f32_wgrad_group(const WgradJob* jobs, int n, hipStream_t st);
+int gemm_f32_wgrad_group(const WgradJob* jobs, int n, hipStream_t st, bool st_is_callers);
 int gemm_f32(const float* A, const float* B, float* C, const float* bias, float* preact, int64_t M,
              int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, bool a_kmajor,
              bool b_kmajor, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int act, float beta,
@@ -50,9 +50,9 @@ static std::vector<WgradJob> g_wq;
 static int g_wq_on = 0;
 bool wgrad_defer_on() { return g_wq_on != 0; }
 static hipStream_t g_wq_stream = nullptr;
-static int wq_flush_locked() {
+static int wq_flush_locked(bool st_is_callers = true) {
     if (g_wq.empty()) return 0;
-    const int rc = gemm_f32_wgrad_group(g_wq.data(), (int)g_wq.size(), g_wq_stream);
+    const int rc = gemm_f32_wgrad_group(g_wq.data(), (int)g_wq.size(), g_wq_stream, st_is_callers);
     g_wq.clear();
     return rc;
 }
@@ -61,7 +61,7 @@ static bool wq_offer(const WgradJob& j, hipStream_t st, int* rc) {
     std::lock_guard<std::mutex> lk(g_wq_mu);
     *rc = 0;
     if (!g_wq_on || !gemm_f32_wgrad_group_ok(j)) return false;
-    if (!g_wq.empty() && g_wq_stream != st) *rc = wq_flush_locked();   // one queue, one stream
+    if (!g_wq.empty() && g_wq_stream != st) *rc = wq_flush_locked(false);   // one queue, one stream
     g_wq_stream = st;
     g_wq.push_back(j);
     return true;
@@ -197,7 +197,8 @@ extern "C" int nnhipWeightGradFlush(nnhipStream_t stream) {
 }
 // Only the queued GEMMs (the grouped launch + its reduce), on `stream` -- which may be a side stream: the launch reads the queued
 // calls' X / dO (the caller orders `stream` behind their producers and keeps them alive until it has joined `stream` again), writes
-// its slabs to a block of its own and dW / db where the calls asked.  The conv reduces and RMSNorm column sums queued next to them
+// its slabs to a block of its own (later users of that block on another stream are ordered behind it: gemm_f32_wgrad_group's
+// guard) and dW / db where the calls asked.  The conv reduces and RMSNorm column sums queued next to them
 // stay for nnhipWeightGradFlush on the stream their producers run on.  ABI 210
 extern "C" int nnhipWeightGradFlushGemms(nnhipStream_t stream) {
     std::lock_guard<std::mutex> lk(g_wq_mu);

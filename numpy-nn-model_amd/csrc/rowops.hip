@@ -15,6 +15,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "deferred_queue.h"
 #include "gemm_small.h"
 
 namespace nnhip {
@@ -430,97 +431,30 @@ __global__ __launch_bounds__(256) void colsum_group_kernel(const ColsumGroup grp
     const ColsumJob jb = grp.j[k];
     colsum_slices<256, SW, VEC>(jb.part, jb.prow, jb.cols, jb.out, (int)blockIdx.x - grp.start[k], grp.start[k + 1] - grp.start[k], lds);
 }
-static std::mutex g_csq_mu;
-static ColsumJob g_csq[CSQ_MAX];
-static int g_csq_n = 0, g_csq_sw = 0;
-static bool g_csq_vec = false;
-static hipStream_t g_csq_st = nullptr;
-static float* g_csq_arena = nullptr;
-static size_t g_csq_cap = 0, g_csq_used = 0;              // floats
-// The arena is ONE per process.  A flush launched on stream A may still be reading it when a backward pass on stream B starts
-// writing partials at offset 0 (advisor, round 5): every flush outside a graph capture records an event, and the first reservation
-// on another stream waits for it.  (Inside a capture the step is single-stream by construction, neunet_hip/graph.py.)
-static hipEvent_t g_csq_ev = nullptr;
-static hipStream_t g_csq_flush_st = nullptr;
-static bool g_csq_ev_live = false;
-static bool csq_capturing(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return cs != hipStreamCaptureStatusNone;
-}
-static int csq_flush_locked(hipStream_t st) {
-    if (g_csq_n == 0) { g_csq_used = 0; return 0; }         // (a reservation whose launch failed leaves nothing queued: give its floats back)
+// jobs of one launch share the slice width and the vector flag: the queue's key (deferred_queue.h)
+static int colsum_group_launch(const ColsumJob* q, int n, int key, hipStream_t st) {
+    const int sw = key >> 1;
+    const bool vec = key & 1;
     ColsumGroup grp;
-    int blocks = 0;
-    for (int i = 0; i < CSQ_MAX; ++i) {
-        grp.start[i] = blocks;
-        if (i < g_csq_n) { grp.j[i] = g_csq[i]; blocks += fin_slices(g_csq[i].cols, g_csq_vec); }
-        else grp.j[i] = g_csq[0];
-    }
-    grp.start[CSQ_MAX] = blocks;
-    g_csq_n = 0;
-    g_csq_used = 0;
+    const int blocks = group_starts<CSQ_MAX>(q, n, grp.j, grp.start, [vec](const ColsumJob& j) { return fin_slices(j.cols, vec); });
 #define CSG(SW_, V_) hipLaunchKernelGGL((colsum_group_kernel<SW_, V_>), dim3((unsigned)blocks), dim3(256), 0, st, grp)
-    if (g_csq_vec) { if (g_csq_sw == 8) CSG(8, true); else CSG(4, true); }
-    else { if (g_csq_sw == 8) CSG(8, false); else CSG(4, false); }
+    if (vec) { if (sw == 8) CSG(8, true); else CSG(4, true); }
+    else { if (sw == 8) CSG(8, false); else CSG(4, false); }
 #undef CSG
     NNHIP_LAUNCH_CHECK("colsum_group_kernel");
-    if (!csq_capturing(st)) {
-        if (!g_csq_ev && hipEventCreateWithFlags(&g_csq_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); g_csq_ev = nullptr; }
-        if (g_csq_ev && hipEventRecord(g_csq_ev, st) == hipSuccess) { g_csq_flush_st = st; g_csq_ev_live = true; }
-        else (void)hipGetLastError();
-    }
     return 0;
 }
-int colsum_flush(void* stream) {
-    std::lock_guard<std::mutex> lk(g_csq_mu);
-    return csq_flush_locked(g_csq_n ? g_csq_st : (hipStream_t)stream);
-}
-void colsum_cleanup() {
-    std::lock_guard<std::mutex> lk(g_csq_mu);
-    g_csq_n = 0;
-    g_csq_used = g_csq_cap = 0;
-    if (g_csq_arena) (void)hipFree(g_csq_arena);
-    g_csq_arena = nullptr;
-}
+static DeferredQueue<ColsumJob, CSQ_MAX> g_csq(colsum_group_launch);
+int colsum_flush(void* stream) { return g_csq.flush((hipStream_t)stream); }
+void colsum_cleanup() { g_csq.cleanup(); }
 // Where a RMSNorm backward writes `floats` of partials whose column sums (`njobs` of them, slice width sw / vec) can wait for the
-// flush: the arena (*deferred), else nullptr (the caller uses the shared workspace and finishes at once).
-static float* colsum_partials(size_t floats, int njobs, int sw, bool vec, hipStream_t st, bool* deferred, int* rc) {
+// flush: the arena, else nullptr (the caller uses the shared workspace and finishes at once).  The arena has room for a whole queue
+// of the same size.
+static float* colsum_partials(size_t floats, int njobs, int sw, bool vec, hipStream_t st, int* rc) {
     static const bool on = []() { const char* e = getenv("NNHIP_COLSUM_DEFER"); return !e || atoi(e) != 0; }();
-    *deferred = false;
     *rc = 0;
     if (!on || !wgrad_defer_on()) return nullptr;
-    std::lock_guard<std::mutex> lk(g_csq_mu);
-    if (g_csq_n && (g_csq_st != st || g_csq_n + njobs > CSQ_MAX || g_csq_used + floats > g_csq_cap || g_csq_sw != sw || g_csq_vec != vec))
-        *rc = csq_flush_locked(g_csq_st);
-    if (g_csq_ev_live && g_csq_flush_st != st && !csq_capturing(st)) {      // the last flush ran on another stream: order behind it
-        if (hipStreamWaitEvent(st, g_csq_ev, 0) != hipSuccess) (void)hipGetLastError();
-        g_csq_flush_st = st;                                                // (this stream is now ordered behind that flush)
-    }
-    if (floats > g_csq_cap && !workspace_locked()) {          // grow (nothing is queued here); never while a captured graph holds the address
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cs);
-        if (cs == hipStreamCaptureStatusNone) {
-            if (g_csq_arena) (void)hipFree(g_csq_arena);      // (synchronises: earlier sums are done with it)
-            g_csq_arena = nullptr;
-            g_csq_cap = 0;
-            const size_t want = floats * CSQ_MAX;              // room for a whole queue of the same size
-            if (hipMalloc(&g_csq_arena, want * sizeof(float)) == hipSuccess) g_csq_cap = want;
-            else g_csq_arena = nullptr;
-        }
-    }
-    if (g_csq_arena && floats <= g_csq_cap - g_csq_used) {
-        float* p = g_csq_arena + g_csq_used;
-        g_csq_used += (floats + 63) & ~(size_t)63;
-        g_csq_st = st; g_csq_sw = sw; g_csq_vec = vec;
-        *deferred = true;
-        return p;
-    }
-    return nullptr;
-}
-static void colsum_queue(const float* part, float* out, int64_t prow, int64_t cols) {
-    std::lock_guard<std::mutex> lk(g_csq_mu);
-    g_csq[g_csq_n++] = ColsumJob{part, out, prow, cols};
+    return g_csq.reserve(floats, njobs, sw << 1 | (vec ? 1 : 0), st, floats * CSQ_MAX, rc);
 }
 
 // ---- the persistent norm backward, shared by RMSNorm and LayerNorm ---------------------------------------------------
@@ -1946,8 +1880,9 @@ static int norm_backward(const float* dY, const float* X, const float* weight, c
     if (nparts) {
         // inside Tensor.backward() the finishing column sums wait for the flush (one launch for every norm of the pass)
         int rcq = 0;
-        part = colsum_partials(part_floats * nparts, nparts, fin_sw(cols, vec), vec, st, &deferred, &rcq);
+        part = colsum_partials(part_floats * nparts, nparts, fin_sw(cols, vec), vec, st, &rcq);
         if (rcq) return rcq;
+        deferred = part != nullptr;
         if (!part) part = static_cast<float*>(workspace(part_floats * nparts * sizeof(float)));
         NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "%s: workspace allocation failed", Entry::entry);
     }
@@ -1960,8 +1895,8 @@ static int norm_backward(const float* dY, const float* X, const float* weight, c
     NNHIP_LAUNCH_CHECK(Entry::rows_name);
     if (nparts == 0) return 0;
     if (deferred) {
-        if (dW) colsum_queue(part_dw, dW, nblk, cols);
-        if (dB) colsum_queue(part_db, dB, nblk, cols);
+        if (dW) g_csq.push(ColsumJob{part_dw, dW, nblk, cols});
+        if (dB) g_csq.push(ColsumJob{part_db, dB, nblk, cols});
         return 0;
     }
     if (dW) return colsum_tall(part_dw, dW, part_db, dB, nblk, cols, vec, st);
@@ -2168,8 +2103,8 @@ namespace nnhip {
 static int ce_launch(CeArgs a, hipStream_t st) {
     unsigned* sync = sync_words();
     if (!sync) { set_last_error("cross entropy: sync words allocation failed"); return NNHIP_ENOMEM; }
-    if (int rc = serialize_shared_state(st)) return rc;     // one ticket word / partial array per process: see runtime.hip
-    const SharedStateUse in_use(st);
+    const StreamGuard::Use in_use = g_shared_state_guard.acquire(st);     // one ticket word / partial array per process
+    if (!in_use) return in_use.rc;
     a.sync = sync + SYNC_CE;
     a.nt = row_streaming(a.rows, a.cols, a.ld);
     float* denom_scratch = reinterpret_cast<float*>(sync + SYNC_CE + 4);
@@ -2292,14 +2227,15 @@ extern "C" int nnhipLinearCrossEntropyLoss(const float* X, const float* W, const
     a.count_out = count_out_or_null;
     a.count_in_kernel = a.mode == 1 ? 1 : 0;
     const unsigned nblk = (unsigned)ceil_div(rows, 16);    // one block per 16 rows
+    StreamGuard::Use in_use;                               // (an unreduced loss touches no shared word: no guard)
     if (a.loss_out) {
         unsigned* sync = sync_words();
         a.partial = static_cast<float*>(workspace((size_t)nblk * sizeof(float)));
         if (!sync || !a.partial) { set_last_error("nnhipLinearCrossEntropyLoss: workspace allocation failed"); return NNHIP_ENOMEM; }
-        if (int rc = serialize_shared_state((hipStream_t)s)) return rc;
+        in_use = g_shared_state_guard.acquire((hipStream_t)s);
+        if (!in_use) return in_use.rc;
         a.sync = sync + SYNC_CE;
     }
-    const SharedStateUse in_use((hipStream_t)s);      // (harmless when the loss is not reduced: an event behind the launch)
     const bool vec = (in_features & 3) == 0 && aligned16(X) && aligned16(W);
     const bool nw8 = ((in_features + 15) >> 4) >= 8;       // gemm_small()'s choice
     hipStream_t st = (hipStream_t)s;
@@ -2351,8 +2287,8 @@ extern "C" int nnhipBatchNorm2dLinearSigmoidMSE(const float* X, const float* sta
     unsigned* sync = sync_words();
     a.partial = static_cast<float*>(workspace((size_t)nblk * sizeof(float)));
     if (!sync || !a.partial) { set_last_error("nnhipBatchNorm2dLinearSigmoidMSE: workspace allocation failed"); return NNHIP_ENOMEM; }
-    if (int rc = serialize_shared_state((hipStream_t)s)) return rc;
-    const SharedStateUse in_use((hipStream_t)s);
+    const StreamGuard::Use in_use = g_shared_state_guard.acquire((hipStream_t)s);
+    if (!in_use) return in_use.rc;
     a.sync = sync + SYNC_CE;
     hipLaunchKernelGGL((bn_linear_sigmoid_mse_kernel<8>), dim3(nblk), dim3(512), 0, (hipStream_t)s, p, h, a);
     NNHIP_LAUNCH_CHECK("bn_linear_sigmoid_mse_kernel");

@@ -77,57 +77,63 @@ const float* zero_block() {
     return z;
 }
 
-// Library-owned device words (arrival tickets, the CE denominator scratch) and the workspace partials behind them are ONE set
-// per process: two launches that use them must not overlap.  On one stream that is program order.  A launch that arrives on a
-// DIFFERENT stream than the previous user is ordered behind everything the device has been given so far (hipDeviceSynchronize):
-// the single-stream assumption is enforced instead of assumed (round-3 review).  The previous caller's stream handle is only ever
-// COMPARED, never used -- it is the caller's object and may be gone by now (CuPy destroys its streams on garbage collection;
-// round-4 advisor: an event recorded on a destroyed stream is undefined behaviour and left the guard failing for the rest of the
-// process).  Costs a pointer compare when the stream is the same; a stream change is rare (a few per process) and pays a device
-// sync.  While `st` is being captured into a hipGraph nothing is inserted (a sync is illegal there; a captured step is
-// single-stream by construction, neunet_hip/graph.py), and a sync refused because ANOTHER stream is capturing is skipped likewise.
-static std::mutex g_ss_mu;
-static hipStream_t g_ss_last = nullptr;
-static bool g_ss_have_last = false;
-static hipEvent_t g_ss_ev = nullptr;        // recorded behind the last user's launches (shared_state_done), outside graph captures
-static bool g_ss_ev_live = false;
-static bool ss_capturing(hipStream_t st) {
+// ---- StreamGuard: stream ordering of library-owned scratch (common.h) --------------------------------------------------------------
+// The sync words with the ticket partials behind them, the column-sum and conv-reduce arenas (deferred_queue.h) and the slabs of the
+// grouped dW launch (workspace block 1) each exist ONCE per process: two launches that use the same piece must not overlap.  On one
+// stream that is program order, and acquire() is a pointer compare.  A user that arrives on ANOTHER stream than the previous one
+// waits for the event the previous user left behind its launches (a library-owned object), or, when there is no live event,
+// for everything the device has been given so far (hipDeviceSynchronize).  There is none when the previous user ran inside a
+// graph capture -- replays of that graph may still be reading the scratch, and an event recorded into a capture is not one a later
+// stream can wait on -- when its stream was a handle kept from an earlier call (a queue flushed because the stream changed), or when
+// the event could not be made.  The previous user's stream handle is only ever COMPARED, never passed to the runtime: it is the
+// caller's object and may be gone by now (CuPy destroys its streams on garbage collection; an event recorded on a destroyed stream
+// is undefined behaviour and once left the guard failing for the rest of the process).  While `st` is being captured nothing is
+// inserted (a sync is illegal there; a captured step is single-stream by construction, neunet_hip/graph.py), and a sync refused
+// because ANOTHER stream is capturing is skipped likewise.
+bool stream_capturing(hipStream_t st) {
     hipStreamCaptureStatus a = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &a) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a != hipStreamCaptureStatusNone;
 }
-int serialize_shared_state(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_ss_mu);
-    if (g_ss_have_last && g_ss_last != st && !ss_capturing(st)) {
-        // round 6 (advisor): the previous user left an EVENT behind its launches (a library-owned object; its stream handle is never
-        // touched again) -- the new stream waits for that event instead of the whole device.  No event (the previous user ran inside a
-        // graph capture, or event creation failed): the device sync of round 5.
-        bool ordered = false;
-        if (g_ss_ev_live) {
-            if (hipStreamWaitEvent(st, g_ss_ev, 0) == hipSuccess) ordered = true;
-            else (void)hipGetLastError();
+StreamGuard::Use StreamGuard::acquire(hipStream_t st, bool st_is_callers) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Use use;
+    if (have_last_ && last_ != st && !(st_is_callers && stream_capturing(st))) {
+        hipError_t e = hipSuccess;
+        if (!(ev_live_ && st_is_callers && hipStreamWaitEvent(st, ev_, 0) == hipSuccess)) {
+            (void)hipGetLastError();              // (a failed wait)
+            e = hipDeviceSynchronize();
         }
-        if (!ordered) {
-            const hipError_t e = hipDeviceSynchronize();
-            if (e != hipSuccess) {
-                (void)hipGetLastError();          // e.g. a capture in progress elsewhere: nothing to order against, carry on
-                if (e != hipErrorStreamCaptureUnsupported && e != hipErrorStreamCaptureImplicit && e != hipErrorStreamCaptureInvalidated)
-                    return hip_status(e, "shared-state guard (device synchronize)");
+        if (e != hipSuccess) {
+            (void)hipGetLastError();              // e.g. a capture in progress elsewhere: nothing to order against, carry on
+            if (e != hipErrorStreamCaptureUnsupported && e != hipErrorStreamCaptureImplicit && e != hipErrorStreamCaptureInvalidated) {
+                use.rc = hip_status(e, "stream guard (device synchronize)");
+                return use;
             }
         }
     }
-    g_ss_last = st;
-    g_ss_have_last = true;
-    return 0;
+    last_ = st;
+    have_last_ = true;
+    use.g_ = this;
+    use.st_ = st;
+    use.callers_ = st_is_callers;
+    return use;
 }
-// called (through SharedStateUse's destructor) after a user of the shared words has enqueued its launches on `st`
-void shared_state_done(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_ss_mu);
-    if (ss_capturing(st)) { g_ss_ev_live = false; return; }      // (an event recorded into a capture is not one a later stream can wait on)
-    if (!g_ss_ev && hipEventCreateWithFlags(&g_ss_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); g_ss_ev = nullptr; }
-    if (g_ss_ev && hipEventRecord(g_ss_ev, st) == hipSuccess) g_ss_ev_live = true;
-    else { (void)hipGetLastError(); g_ss_ev_live = false; }
+void StreamGuard::release(hipStream_t st, bool record) {
+    std::lock_guard<std::mutex> lk(mu_);
+    ev_live_ = false;
+    if (!record || stream_capturing(st)) return;
+    if (!ev_ && hipEventCreateWithFlags(&ev_, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev_ = nullptr; }
+    if (ev_ && hipEventRecord(ev_, st) == hipSuccess) ev_live_ = true;
+    else (void)hipGetLastError();
 }
+void StreamGuard::reset() {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (ev_) (void)hipEventDestroy(ev_);
+    ev_ = nullptr;
+    ev_live_ = false;                            // (the last stream stays known: another one synchronises with the device)
+}
+StreamGuard g_shared_state_guard, g_wgrad_slab_guard;
 
 static unsigned* g_deverr_host = nullptr;
 static unsigned* g_deverr_dev = nullptr;
@@ -222,6 +228,8 @@ extern "C" const char* nnhipGetLastErrorString(void) { return nnhip::g_err; }
 extern "C" int nnhipCleanup(void) {
     nnhip::conv_reduce_cleanup();
     nnhip::colsum_cleanup();
+    nnhip::g_shared_state_guard.reset();
+    nnhip::g_wgrad_slab_guard.reset();
     std::lock_guard<std::mutex> lk(nnhip::g_ws_mu);
     nnhip::g_ws_locked = false;
     int rc = 0;

@@ -78,7 +78,7 @@ def test_fused_chain_agrees_with_oracle(name, d, why, alpha):
 # ===================================================================================================== coverage
 # Every kernel instantiation the host code of conv2d.hip / conv_mfma.hip can launch on behalf of Conv2d, from the hipLaunchKernelGGL and
 # launch_* sites (nnhipConv2dForward, conv_pool_forward, nnhipConv2dBackward, nnhipConv2dWeightGradPooled, launch_conv_tap,
-# conv_mfma_wgrad, conv_reduce, crq_flush_locked).
+# conv_mfma_wgrad, conv_reduce, conv_reduce_group_launch).
 WANTED = [
     "conv_direct_fwd_kernel<4>", "conv_direct_fwd_kernel<8>", "conv_direct_fwd_kernel<16>", "conv_direct_fwd_quad_kernel<8>",
     "conv_direct_fwd_quad_kernel<16>", "conv_direct_dgrad_kernel<4>", "conv_direct_dgrad_kernel<8>", "conv_direct_dgrad_kernel<16>",
@@ -105,7 +105,7 @@ WANTED = [
     "conv_wgrad_mfma_kernel<2,128,true,false>", "conv_wgrad_mfma_kernel<2,128,true,true>",
 ]
 # launched, but chosen by the state of the deferred-reduce queue, not by a descriptor: test_conv_tiers_gpu.py::test_deferred_reduce_queue
-NOT_BY_DESCRIPTOR = {"conv_wgrad_reduce_group_kernel": "two or more queued reduces at a flush (crq_flush_locked); no descriptor selects it"}
+NOT_BY_DESCRIPTOR = {"conv_wgrad_reduce_group_kernel": "two or more queued reduces at a flush (conv_reduce_group_launch); no descriptor selects it"}
 # instantiated and launchable by the host code, but no descriptor reaches them: none.  (conv_mfma_wgrad_kernel's 2 x 2 POOL branch on the
 # general path needs an odd nXp = Cin Hp Wp next to an even Wo; unit stride makes Wp = Wo + 2 even, stride 2 makes it odd: pw_c3_22_oddnxp.)
 UNREACHABLE = {}

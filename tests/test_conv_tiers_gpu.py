@@ -337,7 +337,7 @@ def test_deferred_reduce_queue(hip):
     """nnhipWeightGradDefer on: 1 queued small-channel wgrad (conv_wgrad_reduce_kernel), 2 and 4 (conv_wgrad_reduce_group_kernel, a full
     queue), 5 (the fifth flushes the four before it), a job larger than the arena (it grows), and jobs on a second stream.  A stream
     change flushes what the first stream queued, and the arena is reused from offset 0: the new stream must not overwrite partials the
-    flushed reduce has yet to read.  conv_partials orders the new stream behind that reduce with an event (it did not: the kernels of
+    flushed reduce has yet to read.  The queue's guard orders the new stream behind that reduce (it did not: the kernels of
     one nnhipConv2dBackward call went to two unordered streams); the steps here run without any synchronisation in between, so a
     missing order shows as a wrong or NaN gradient whenever the timing allows.  Every dW / db is bit-identical to the same call with
     deferral off ("same arithmetic, same order per output")."""
@@ -384,7 +384,7 @@ def test_deferred_reduce_queue(hip):
         call("nnhipWeightGradFlush")
         check(queued)
         # a stream change: the two reduces queued on the default stream are flushed there and the new job's partials go to offset 0 of the same
-        # arena from `side`.  No synchronisation here: conv_partials orders `side` behind the flushed reduce itself (until it did, the
+        # arena from `side`.  No synchronisation here: the queue's guard orders `side` behind the flushed reduce itself (until it did, the
         # kernel on `side` could overwrite partials the reduce on the default stream had yet to read)
         fs = ready(2, 3, 4)
         queued = [queue(*jobs[2], f=fs[0]), queue(*jobs[3], f=fs[1]), queue(*jobs[4], stream=side.cuda_stream, f=fs[2])]
@@ -407,6 +407,39 @@ def test_deferred_reduce_queue(hip):
             del keep
     finally:
         call("nnhipWeightGradDefer", 0)
+
+
+def test_deferred_reduce_queue_after_its_stream_is_destroyed(hip):
+    """A reduce queued and flushed on a stream that is then synchronised and DESTROYED, the next one on the default stream: the arena's
+    guard only compares the old handle.  (It used to record an event on it and ask whether it was capturing: undefined behaviour.)"""
+    import ctypes
+    import gc
+    n, d = "nt_c1_o7", BY_NAME["nt_c1_o7"].desc
+    X, Wt, _, dO = make_inputs(n, d)
+    ins = (dev(X), dev(Wt), dev(dO))
+    base, _ = backward(d, *ins, want=("dW", "db"))
+    fs = [dict(dW=FencedAt((d.Cout, d.Cin, 3, 3)), db=FencedAt((d.Cout,))) for _ in range(2)]
+    hiprt = ctypes.CDLL("libamdhip64.so")
+    raw = ctypes.c_void_p()
+    assert hiprt.hipStreamCreate(ctypes.byref(raw)) == 0
+    st = torch.cuda.ExternalStream(raw.value)
+    torch.cuda.synchronize()
+    call("nnhipWeightGradDefer", 1)
+    try:
+        assert call("nnhipConv2dBackward", *ins, None, fs[0]["dW"].view, fs[0]["db"].view, cdesc(d), stream=raw.value) == 0
+        assert call("nnhipWeightGradFlush", stream=raw.value) == 0
+        st.synchronize()
+        del st
+        gc.collect()
+        assert hiprt.hipStreamDestroy(raw) == 0
+        assert call("nnhipConv2dBackward", *ins, None, fs[1]["dW"].view, fs[1]["db"].view, cdesc(d)) == 0
+        assert call("nnhipWeightGradFlush") == 0
+    finally:
+        call("nnhipWeightGradDefer", 0)
+    torch.cuda.synchronize()
+    for f, where in zip(fs, ("on the stream destroyed since", "on the default stream behind it")):
+        assert f["dW"].guards_intact() and f["db"].guards_intact()
+        assert torch.equal(f["dW"].view, base["dW"].view) and torch.equal(f["db"].view, base["db"].view), f"{where}: deferred reduce differs"
         torch.cuda.synchronize()
 
 

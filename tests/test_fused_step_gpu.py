@@ -678,7 +678,7 @@ def test_bn_head_refusals(hip):
 
 # ==================================================================================================== two streams
 def test_adam_alternating_streams(hip, two_streams):
-    """The three entries share one set of library words (arrival board, ticket, exchange word) behind serialize_shared_state: the same
+    """The three entries share one set of library words (arrival board, ticket, exchange word) behind one StreamGuard (runtime.hip): the same
     call issued alternately on two streams leaves the single-stream bits."""
     shape, axes = F.MLP_ADAM_SHAPES[1], (1, 1e-2, 5, 1.0, None)
     h = Handle(axes)
@@ -709,6 +709,25 @@ def test_linear_ce_alternating_streams(hip, two_streams):
     for k, o in enumerate(outs):
         assert all(b.intact() for b in o.values())
         same_bits({n: b.host() for n, b in o.items()}, {n: want[n] for n in o}, f"launch {k} on stream {k % 2}")
+
+
+def test_linear_ce_unreduced_call_between_reduced_ones(hip, two_streams):
+    """Stream A reduced, stream B unreduced ('n': no loss output, no shared word), stream B reduced, stream A reduced, twice over
+    with no host synchronisation.  The unreduced call must not count as a user of the shared words: it used to re-record the guard's
+    event on B without becoming the last stream, and the reduced call behind it on B then waited for its own stream instead of A."""
+    run = LinCe((32, 64, 10, 0, 0))                                              # two blocks: the exchange word
+    want = {"m": run.run("m", True, -100), "n": run.run("n", True, -100)}
+    a, b = two_streams
+    seq = [(a, "m"), (b, "n"), (b, "m"), (a, "m")] * 2
+    outs = [run.outputs() for _ in seq]
+    torch.cuda.synchronize()
+    for (st, red), o in zip(seq, outs):
+        with torch.cuda.stream(st):
+            run.launch(o, None, red, True, -100)
+    torch.cuda.synchronize()
+    for k, ((st, red), o) in enumerate(zip(seq, outs)):
+        assert all(buf.intact() for buf in o.values())
+        same_bits({n: buf.host() for n, buf in o.items()}, {n: want[red][n] for n in o}, f"launch {k} ('{red}' on stream {'AB'[st is b]})")
 
 
 def test_bn_head_alternating_streams(hip, two_streams):
