@@ -1085,7 +1085,95 @@ int nnhipStridedCopy(float* out, const float* in, float scale, int rank, const i
 #define NNHIP_TIER_RED_ROW_BLOCK 11
 #define NNHIP_TIER_RED_COL 12
 #define NNHIP_TIER_RED_GENERAL 13
+#define NNHIP_TIER_IDX_VEC4 20          /* compare / logical / where forward: four results per lane */
+#define NNHIP_TIER_IDX_GENERAL 21       /* the strided tier of csrc/tensor_index.hip (also: typed copy, strided / masked assign) */
+#define NNHIP_TIER_SLICE_BWD_VEC 22     /* nnhipSliceBackward: float4 stores */
+#define NNHIP_TIER_SLICE_BWD_SCALAR 23
+#define NNHIP_TIER_IDX_ROW_VEC 24       /* gather / index assign: a wave per row, 16 bytes per lane */
+#define NNHIP_TIER_IDX_ROW 25           /* a wave per row, one element per lane */
+#define NNHIP_TIER_IDX_ELEMENT 26       /* inner == 1: a lane per output */
 int nnhipTensorOpsLastTier(int64_t* segments);
+
+/* ---- the rest of the Tensor tape (ABI 224; neunet/autograd.py:642-808, 895-923): comparisons, logical ops, where, indexing ----------
+ * csrc/tensor_index.hip.  The rules of the section above hold: shapes and strides by value (rank <= 8, <= 6 groups after collapsing),
+ * status codes for bad arguments, a zero-size problem returns 0 without a launch, no float atomics, reruns bit-identical, every entry
+ * may be captured.  Strides are SIGNED element strides; an element offset is an argument (`offset`), added to the base inside the
+ * entry.  Element types travel as NNHIP_DT_*; bool storage is one byte holding 0 or 1.  Pointers are aligned to their element size
+ * (NNHIP_EALIGN).  nnhipTensorOpsLastTier reports the tier of the last launch of these entries too.
+ *
+ * nnhipCompare: out (bytes, contiguous over shape) = a (kind) b.  a and b share `dtype`; a or b (not both) may be NULL: that operand is
+ *   the by-value scalar -- `scalar_i64` when scalar_is_int, else `scalar`.  NumPy 2's rules: against float32 the scalar is rounded to
+ *   float32 first; an integer (or bool) tensor against an integer scalar compares in int64, against a floating scalar in double.  A NaN
+ *   makes every kind false except NE; -0.0 == 0.0.
+ * nnhipLogical: truth is value != 0 (a NaN is true); the operands may differ in dtype; b is ignored for NOT. */
+#define NNHIP_DT_F32 0
+#define NNHIP_DT_I32 1
+#define NNHIP_DT_I64 2
+#define NNHIP_DT_U8 3                   /* bool and uint8 */
+#define NNHIP_CMP_EQ 0
+#define NNHIP_CMP_NE 1
+#define NNHIP_CMP_GT 2
+#define NNHIP_CMP_GE 3
+#define NNHIP_CMP_LT 4
+#define NNHIP_CMP_LE 5
+#define NNHIP_LOGICAL_AND 0
+#define NNHIP_LOGICAL_OR 1
+#define NNHIP_LOGICAL_NOT 2
+int nnhipCompare(int kind, uint8_t* out, const void* a, const void* b, double scalar, int64_t scalar_i64, int scalar_is_int, int dtype,
+                 int rank, const int64_t* shape, const int64_t* stride_a, const int64_t* stride_b, nnhipStream_t stream);
+int nnhipLogical(int kind, uint8_t* out, const void* a, const void* b, int dtype_a, int dtype_b, int rank, const int64_t* shape,
+                 const int64_t* stride_a, const int64_t* stride_b, nnhipStream_t stream);
+/* nnhipWhereForward: out (float32, contiguous over shape) = cond ? a : b.  cond (NNHIP_DT_U8, _I32 or _F32; truth is != 0) broadcasts
+ *   against both operands through stride_c; a and / or b may be NULL: scalar_a / scalar_b.
+ * nnhipWhereBackward: dA = cond ? g : 0, dB = cond ? 0 : g -- a select, so an inf or a NaN of g at a position the operand did not supply
+ *   gives exactly 0.  Each gradient is contiguous in the operand's OWN shape (extent 1 where its stride is 0; a one-element operand gets
+ *   a one-element gradient): the sum over its broadcast axes happens inside the launch that forms it (the reduction kernels with the
+ *   select as their load functor, as nnhipBroadcastBinaryBackward).  Either output may be NULL (its strides are then not read). */
+int nnhipWhereForward(float* out, const void* cond, int cond_dtype, const float* a, const float* b, float scalar_a, float scalar_b, int rank,
+                      const int64_t* shape, const int64_t* stride_c, const int64_t* stride_a, const int64_t* stride_b, nnhipStream_t stream);
+int nnhipWhereBackward(float* dA, float* dB, const float* grad, const void* cond, int cond_dtype, int rank, const int64_t* shape,
+                       const int64_t* stride_c, const int64_t* stride_a, const int64_t* stride_b, nnhipStream_t stream);
+/* nnhipSliceForward: out[shape] (contiguous) = in[offset + sum_i c_i stride_in[i]]: the forward of __getitem__ with a basic key and of
+ *   flip, and flip's backward.  Strides may be negative or 0; the caller guarantees that every address lies inside `in`.  4-byte elements
+ *   take the elementwise copy of the section above (never its LDS tile tier), 1- and 8-byte elements a typed general kernel.
+ *   (nnhipStridedCopy keeps its contract -- non-negative use by transpose / swapaxes, no offset -- and its tiers unchanged.)
+ * nnhipSliceBackward: dX[x_shape] (contiguous float32) from grad (contiguous over count): ONE launch that writes every element of dX
+ *   exactly once -- grad[j] where the element's coordinate is start + j * step with 0 <= j < count on every axis, 0 elsewhere.
+ *   step may be negative (never 0); an axis taken by an integer has count 1.  A lattice that leaves the tensor is NNHIP_EINVAL.
+ * nnhipStridedAssign: out[offset + sum_i c_i stride_out[i]] = in[sum_i c_i stride_in[i]] over shape (in == NULL: the scalar, converted
+ *   to dtype; stride_in may be 0 on broadcast axes; stride_out is never 0 on an axis of extent > 1).  One launch. */
+int nnhipSliceForward(void* out, const void* in, int64_t offset, int dtype, int rank, const int64_t* shape, const int64_t* stride_in,
+                      nnhipStream_t stream);
+int nnhipSliceBackward(float* dX, const float* grad, int rank, const int64_t* x_shape, const int64_t* start, const int64_t* step,
+                       const int64_t* count, nnhipStream_t stream);
+int nnhipStridedAssign(void* out, int64_t offset, const int64_t* stride_out, const void* in, const int64_t* stride_in, double scalar,
+                       int64_t scalar_i64, int scalar_is_int, int dtype, int rank, const int64_t* shape, nnhipStream_t stream);
+/* Integer-array indexing on adjacent axes: x as [outer, D1..Dk, inner], k <= NNHIP_INDEX_MAX_ARRAYS index arrays of M elements each
+ * (idx: a HOST array of k device pointers, all NNHIP_DT_I32 or all NNHIP_DT_I64; dims: D1..Dk), M < 2^31.  Negative indices wrap inside
+ * the kernels.  An index outside its axis is NOT an error here (a device index tensor cannot be checked without a host read): the gather
+ * reads 0 for it and the assign skips it -- nnhipEmbeddingForward's rule.  The host checks the indices it can see.
+ * nnhipIndexGather: out [outer, M, inner] (contiguous) = x[o, idx_1[m], .., idx_k[m], :].  One launch.
+ * nnhipIndexAssign: dst [outer, D1..Dk, inner] <- src [outer, M, inner] (src == NULL: the scalar), last occurrence in C order wins (the
+ *   reference ASSIGNS, also in its backward: `_grad[index] = grad`).  zero_fill != 0 (the gather's backward): every element of dst is
+ *   written once, 0 where no index points; zero_fill == 0 (__setitem__): untouched elements are left alone.  Three launches: the `last`
+ *   table over D1*..*Dk in the library workspace (nnhipWorkspaceReserve before a capture) is filled with -1 on every call, an integer
+ *   atomicMax of the positions, one pass over dst.  The table takes 4 * D1 * .. * Dk bytes of the grow-only workspace -- the WHOLE indexed
+ *   extent, not the M positions: for x[arange(N), y] on [N, C] that is 4 N C bytes (983 MB at [16384, 15000]), as much as x itself.  A
+ *   call that needs more than the workspace holds grows it (a device synchronisation and an allocation: not legal inside a capture);
+ *   under nnhipWorkspaceLock it returns NNHIP_ENOMEM instead.  Reserve at least that many bytes with nnhipWorkspaceReserve before
+ *   capturing a call.
+ * nnhipMaskedAssign: dst [rows, inner]; dst[r, :] = value [inner] (NULL: the scalar) where mask[r] != 0.  One launch, no compaction. */
+#define NNHIP_INDEX_MAX_ARRAYS 4
+int nnhipIndexGather(void* out, const void* x, int dtype, const void* const* idx, int idx_dtype, int k, const int64_t* dims, int64_t outer,
+                     int64_t M, int64_t inner, nnhipStream_t stream);
+int nnhipIndexAssign(void* dst, const void* src, double scalar, int64_t scalar_i64, int scalar_is_int, int dtype, int zero_fill,
+                     const void* const* idx, int idx_dtype, int k, const int64_t* dims, int64_t outer, int64_t M, int64_t inner,
+                     nnhipStream_t stream);
+int nnhipMaskedAssign(void* dst, const uint8_t* mask, const void* value, double scalar, int64_t scalar_i64, int scalar_is_int, int dtype,
+                      int64_t rows, int64_t inner, nnhipStream_t stream);
+/* np.argmin on nnhipArgmaxF32's kernels with the mirrored order: the FIRST minimum wins, a NaN wins.  Arguments and status as
+ * nnhipArgmaxF32. */
+int nnhipArgminF32(int32_t* out, const float* x, int64_t outer, int64_t n, int64_t inner, nnhipStream_t stream);
 
 #ifdef __cplusplus
 }

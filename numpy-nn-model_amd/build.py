@@ -18,8 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip", "tensor_ops.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"), os.path.join(CSRC, "ew_map.h"), os.path.join(CSRC, "deferred_queue.h"),
+SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip", "tensor_ops.hip", "tensor_index.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"), os.path.join(CSRC, "ew_map.h"), os.path.join(CSRC, "deferred_queue.h"), os.path.join(CSRC, "tensor_ops.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
 
@@ -66,7 +66,12 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             # in registers between var's two sweeps): a spill would put them in scratch.  The general reduction tier indexes its shape
             # description at run time and is for correctness only: exempt
             "tensor_ops.hip": (r"ew_vec2d_kernel", r"ew_general_kernel", r"red_row_wave_kernel", r"red_row_block_kernel", r"red_col_kernel",
-                               r"red_finish_kernel", r"transpose_tile_kernel", r"map1s_kernel", r"map2_kernel")}
+                               r"red_finish_kernel", r"transpose_tile_kernel", r"map1s_kernel", r"map2_kernel"),
+            # comparisons, selects and copies: streaming loads and stores and nothing else, so a spill would be pure extra traffic.  The
+            # where-gradients are tensor_ops.h's elementwise and structured reduction kernels; its general reduction tier is exempt as above
+            "tensor_index.hip": (r"cmp_", r"logical_", r"where_", r"copy_general_kernel", r"assign_kernel", r"slice_bwd_kernel", r"gather_",
+                                 r"index_", r"masked_assign_kernel", r"ew_vec2d_kernel", r"ew_general_kernel", r"red_row_wave_kernel",
+                                 r"red_row_block_kernel", r"red_col_kernel", r"red_finish_kernel")}
 # The 2-wave-block attention kernels (head dim 64) sit exactly at the 256-VGPR limit of 2 waves per SIMD and keep two or
 # three values in scratch (8-12 B/lane; measured 4-6 % FASTER than the 4-wave blocks all the same): tolerated up to here.
 SPILL_ALLOWANCE = ((r"attn_\w+_kernelILi64ELb0ELi2E", 16),

@@ -108,7 +108,9 @@ __device__ __forceinline__ ArgBest arg_wave_reduce(ArgBest b) {
 
 // last-axis rows (inner == 1): blockDim = 256; ROWS_PER_BLOCK = 4 (one wave per row, n <= 4096) or 1 (the block strides the row).
 // chunks > 1 (one long row, e.g. axis=None): block (row, c) scans its slice and writes a partial pair; arg_finish_kernel closes.
-template <int RPB>
+// MIN: np.argmin -- the same kernels on the mirrored order of arg_order.h, i.e. on the negated values (exact, keeps a NaN a NaN): the first
+// minimum wins, a NaN wins.  The partial values of a chunked row are stored negated, so arg_finish_kernel serves both.
+template <int RPB, bool MIN>
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int32_t* __restrict__ out, int64_t rows,
                                                           int64_t n, int chunks, float* __restrict__ pv, int32_t* __restrict__ pi) {
     __shared__ float sv[4];
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
         if (r >= rows) return;
         const float* p = x + r * n;
         for (int64_t i = lane; i < n; i += 64) {
-            const float v = p[i];
+            const float v = MIN ? -p[i] : p[i];
             if (arg_better(v, (int32_t)i, b.v, b.i)) { b.v = v; b.i = (int32_t)i; }
         }
         b = arg_wave_reduce(b);
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
         const int64_t per = (n + chunks - 1) / chunks, lo = c * per, hi = lo + per < n ? lo + per : n;
         const float* p = x + r * n;
         for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-            const float v = p[i];
+            const float v = MIN ? -p[i] : p[i];
             if (arg_better(v, (int32_t)i, b.v, b.i)) { b.v = v; b.i = (int32_t)i; }
         }
         b = arg_wave_reduce(b);
@@ -159,6 +161,7 @@ __global__ __launch_bounds__(64) void arg_finish_kernel(const float* __restrict_
     if (threadIdx.x == 0) out[r] = b.i;
 }
 // inner > 1: one thread per output element (o, j), walking n with stride `inner` (coalesced across j)
+template <bool MIN>
 __global__ __launch_bounds__(256) void argmax_strided_kernel(const float* __restrict__ x, int32_t* __restrict__ out,
                                                              int64_t outer, int64_t n, int64_t inner) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(256) void argmax_strided_kernel(const float* __rest
     const float* p = x + o * n * inner + j;
     ArgBest b{-INFINITY, 0x7fffffff};
     for (int64_t i = 0; i < n; ++i) {
-        const float v = p[i * inner];
+        const float v = MIN ? -p[i * inner] : p[i * inner];
         if (arg_better(v, (int32_t)i, b.v, b.i)) { b.v = v; b.i = (int32_t)i; }
     }
     out[t] = b.i;
@@ -223,20 +226,21 @@ extern "C" int nnhipNotEqualInt32(int32_t* out, const int32_t* ids, int64_t n, i
     return 0;
 }
 
-extern "C" int nnhipArgmaxF32(int32_t* out, const float* x, int64_t outer, int64_t n, int64_t inner, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(outer >= 0 && n >= 0 && inner >= 0, NNHIP_EINVAL, "nnhipArgmaxF32: negative size");
-    NNHIP_CHECK_ARG(n > 0 || outer * inner == 0, NNHIP_EINVAL, "nnhipArgmaxF32: attempt to get argmax of an empty sequence");
-    NNHIP_CHECK_ARG(n < ((int64_t)1 << 31), NNHIP_EINVAL, "nnhipArgmaxF32: axis longer than int32 indices can address");
+template <bool MIN>
+static int arg_extreme(const char* fn, int32_t* out, const float* x, int64_t outer, int64_t n, int64_t inner, nnhipStream_t s) {
+    NNHIP_CHECK_ARG(outer >= 0 && n >= 0 && inner >= 0, NNHIP_EINVAL, "%s: negative size", fn);
+    NNHIP_CHECK_ARG(n > 0 || outer * inner == 0, NNHIP_EINVAL, "%s: attempt to get %s of an empty sequence", fn, MIN ? "argmin" : "argmax");
+    NNHIP_CHECK_ARG(n < ((int64_t)1 << 31), NNHIP_EINVAL, "%s: axis longer than int32 indices can address", fn);
     if (outer * inner == 0) return 0;
-    NNHIP_CHECK_ARG(out && x, NNHIP_EINVAL, "nnhipArgmaxF32: null pointer");
+    NNHIP_CHECK_ARG(out && x, NNHIP_EINVAL, "%s: null pointer", fn);
     hipStream_t st = (hipStream_t)s;
     if (inner > 1) {
-        hipLaunchKernelGGL(argmax_strided_kernel, dim3((unsigned)ceil_div(outer * inner, 256)), dim3(256), 0, st, x, out, outer, n, inner);
+        hipLaunchKernelGGL(argmax_strided_kernel<MIN>, dim3((unsigned)ceil_div(outer * inner, 256)), dim3(256), 0, st, x, out, outer, n, inner);
         NNHIP_LAUNCH_CHECK("argmax_strided_kernel");
         return 0;
     }
     if (n <= 4096 && outer >= 4) {
-        hipLaunchKernelGGL(argmax_rows_kernel<4>, dim3((unsigned)ceil_div(outer, 4)), dim3(256), 0, st, x, out, outer, n, 1, nullptr, nullptr);
+        hipLaunchKernelGGL((argmax_rows_kernel<4, MIN>), dim3((unsigned)ceil_div(outer, 4)), dim3(256), 0, st, x, out, outer, n, 1, nullptr, nullptr);
         NNHIP_LAUNCH_CHECK("argmax_rows_kernel");
         return 0;
     }
@@ -248,20 +252,28 @@ extern "C" int nnhipArgmaxF32(int32_t* out, const float* x, int64_t outer, int64
         if (chunks > cap) chunks = (int)cap;
         if (chunks < 1) chunks = 1;
     }
-    NNHIP_CHECK_ARG(outer * chunks < ((int64_t)1 << 31), NNHIP_EINVAL, "nnhipArgmaxF32: too many rows");
+    NNHIP_CHECK_ARG(outer * chunks < ((int64_t)1 << 31), NNHIP_EINVAL, "%s: too many rows", fn);
     float* pv = nullptr;
     int32_t* pi = nullptr;
     if (chunks > 1) {
         void* ws = workspace((size_t)outer * chunks * 8);
-        NNHIP_CHECK_ARG(ws != nullptr, NNHIP_ENOMEM, "nnhipArgmaxF32: workspace allocation failed");
+        NNHIP_CHECK_ARG(ws != nullptr, NNHIP_ENOMEM, "%s: workspace allocation failed", fn);
         pv = static_cast<float*>(ws);
         pi = reinterpret_cast<int32_t*>(pv + outer * chunks);
     }
-    hipLaunchKernelGGL(argmax_rows_kernel<1>, dim3((unsigned)(outer * chunks)), dim3(256), 0, st, x, out, outer, n, chunks, pv, pi);
+    hipLaunchKernelGGL((argmax_rows_kernel<1, MIN>), dim3((unsigned)(outer * chunks)), dim3(256), 0, st, x, out, outer, n, chunks, pv, pi);
     NNHIP_LAUNCH_CHECK("argmax_rows_kernel");
     if (chunks > 1) {
         hipLaunchKernelGGL(arg_finish_kernel, dim3((unsigned)outer), dim3(64), 0, st, pv, pi, out, chunks);
         NNHIP_LAUNCH_CHECK("arg_finish_kernel");
     }
     return 0;
+}
+
+extern "C" int nnhipArgmaxF32(int32_t* out, const float* x, int64_t outer, int64_t n, int64_t inner, nnhipStream_t s) {
+    return arg_extreme<false>("nnhipArgmaxF32", out, x, outer, n, inner, s);
+}
+
+extern "C" int nnhipArgminF32(int32_t* out, const float* x, int64_t outer, int64_t n, int64_t inner, nnhipStream_t s) {
+    return arg_extreme<true>("nnhipArgminF32", out, x, outer, n, inner, s);
 }

@@ -19,10 +19,10 @@ def tensor(data, requires_grad=True, dtype=np.float32, device="cpu"):
     return Tensor(data, requires_grad=requires_grad, dtype=dtype, device=device)
 
 
-def argmax(x: Tensor, axis=None, keepdims=False):
-    """neunet.argmax -> int32 (neunet/__init__.py:132-139); index results must be bit-exact."""
+def _arg_extreme(x: Tensor, axis, keepdims, which):
+    """argmax / argmin -> int32; `which`: 'argmax' | 'argmin' (np.<which>, torch.<which>, nnhipArgmaxF32 / nnhipArgminF32)."""
     if x.device == "cpu":
-        out = np.argmax(x.data, axis=axis, keepdims=keepdims).astype(np.int32)
+        out = getattr(np, which)(x.data, axis=axis, keepdims=keepdims).astype(np.int32)
         return Tensor(out, dtype=np.int32, requires_grad=False, device="cpu")
     import torch
     from ._lib import call_hip_function, get_current_stream_ptr
@@ -35,7 +35,8 @@ def argmax(x: Tensor, axis=None, keepdims=False):
         if d.dtype in (torch.int16, torch.uint8, torch.bool):
             d = d.to(torch.float32)
         else:
-            out = torch.argmax(d) if axis is None else torch.argmax(d, dim=axis, keepdim=keepdims)
+            fn = getattr(torch, which)
+            out = fn(d) if axis is None else fn(d, dim=axis, keepdim=keepdims)
             if axis is None and keepdims:
                 out = out.reshape((1,) * d.dim())
             return Tensor(out.to(torch.int32), dtype=np.int32, requires_grad=False, device="cuda")
@@ -50,10 +51,76 @@ def argmax(x: Tensor, axis=None, keepdims=False):
         outer, n, inner = int(np.prod(shape[:ax], dtype=np.int64)), shape[ax], int(np.prod(shape[ax + 1:], dtype=np.int64))
         oshape = shape[:ax] + ((1,) if keepdims else ()) + shape[ax + 1:]
     if n == 0 and outer * inner > 0:
-        raise ValueError("attempt to get argmax of an empty sequence")
+        raise ValueError(f"attempt to get {which} of an empty sequence")
     out = torch.empty(oshape, dtype=torch.int32, device=d.device)
-    call_hip_function("nnhipArgmaxF32", out, d, outer, n, inner, get_current_stream_ptr())
+    call_hip_function("nnhipArgmaxF32" if which == "argmax" else "nnhipArgminF32", out, d, outer, n, inner, get_current_stream_ptr())
     return Tensor(out, dtype=np.int32, requires_grad=False, device="cuda")
+
+
+def argmax(x: Tensor, axis=None, keepdims=False):
+    """neunet.argmax -> int32 (neunet/__init__.py:132-139); index results must be bit-exact."""
+    return _arg_extreme(x, axis, keepdims, "argmax")
+
+
+def argmin(x: Tensor, axis=None, keepdims=False):
+    """neunet.argmin -> int32 (neunet/__init__.py:142-149): the first minimum wins, a NaN wins (np.argmin); nnhipArgminF32."""
+    return _arg_extreme(x, axis, keepdims, "argmin")
+
+
+# ---- constructors (neunet/__init__.py:45-129, 283-287): the reference's signatures and defaults (requires_grad=False, float32, "cpu") ----
+def _normalize_shape(shape):
+    return tuple(*shape) if shape and all(isinstance(a, (list, tuple)) for a in shape) else tuple(shape)
+
+
+def _filled(data, dtype, requires_grad, device):
+    return Tensor(data, requires_grad=requires_grad, dtype=dtype, device="cpu" if device is None else device)
+
+
+def ones(*shape, dtype=None, requires_grad=False, device=None):
+    dtype = np.float32 if dtype is None else dtype
+    return _filled(np.ones(_normalize_shape(shape), dtype=dtype), dtype, requires_grad, device)
+
+
+def zeros(*shape, dtype=None, requires_grad=False, device=None):
+    dtype = np.float32 if dtype is None else dtype
+    return _filled(np.zeros(_normalize_shape(shape), dtype=dtype), dtype, requires_grad, device)
+
+
+def rand(*shape, dtype=None, requires_grad=False, device=None):
+    """Uniform [0, 1) from np.random on the host (the reference's CPU path), then moved."""
+    dtype = np.float32 if dtype is None else dtype
+    return _filled(np.random.rand(*_normalize_shape(shape)).astype(dtype), dtype, requires_grad, device)
+
+
+def randn(*shape, dtype=None, requires_grad=False, device=None):
+    dtype = np.float32 if dtype is None else dtype
+    return _filled(np.random.randn(*_normalize_shape(shape)).astype(dtype), dtype, requires_grad, device)
+
+
+def arange(start=0, end=None, step=1, dtype=None, requires_grad=False, device=None):
+    if end is None:
+        start, end = 0, start
+    dtype = np.float32 if dtype is None else dtype
+    return _filled(np.arange(start, end, step, dtype=dtype), dtype, requires_grad, device)
+
+
+def ones_like(tensor, dtype=None, requires_grad=False, device=None):       # noqa: A002  (the reference's argument name)
+    dtype = tensor.dtype if dtype is None else dtype
+    return _filled(np.ones(tensor.shape, dtype=dtype), dtype, requires_grad, tensor.device if device is None else device)
+
+
+def zeros_like(tensor, dtype=None, requires_grad=False, device=None):      # noqa: A002
+    dtype = tensor.dtype if dtype is None else dtype
+    return _filled(np.zeros(tensor.shape, dtype=dtype), dtype, requires_grad, tensor.device if device is None else device)
+
+
+def copy(x: Tensor) -> Tensor:
+    """A new leaf with a copy of the data (Tensor.__init__ copies)."""
+    return Tensor(x.data, requires_grad=x.requires_grad, dtype=x.dtype, device=x.device)
+
+
+def clone(x: Tensor) -> Tensor:
+    return copy(x)
 
 
 SAMPLE_MAX_K = 1024      # NNHIP_SAMPLE_MAX_K (include/neunet_hip.h)
@@ -483,3 +550,50 @@ def transpose(x, *axes):
 
 def swapaxes(x, axis1, axis2):
     return x.swapaxes(axis1, axis2)
+
+
+# ---- comparisons, logical ops, where, flip as functions (neunet/__init__.py:249-281); see neunet_hip/tensor_index.py ---------------------
+def flip(x, axis):
+    return x.flip(axis=axis)
+
+
+def where(condition, x, y):
+    """np.where(condition, x, y): x and y float32 Tensors or scalars (a scalar travels by value, it becomes no tensor)."""
+    from .tensor_index import where as _where
+    return _where(condition, x, y)
+
+
+def equal(x, y):
+    return x.equal(y)
+
+
+def not_equal(x, y):
+    return x.not_equal(y)
+
+
+def greater(x, y):
+    return x.greater(y)
+
+
+def greater_equal(x, y):
+    return x.greater_equal(y)
+
+
+def less(x, y):
+    return x.less(y)
+
+
+def less_equal(x, y):
+    return x.less_equal(y)
+
+
+def logical_and(x, y):
+    return x.logical_and(y)
+
+
+def logical_or(x, y):
+    return x.logical_or(y)
+
+
+def logical_not(x):
+    return x.logical_not()

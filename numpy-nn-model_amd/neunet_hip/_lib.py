@@ -253,6 +253,24 @@ _SIGNATURES = {
     "nnhipReduceAxesBackward": (ctypes.c_int, [ctypes.c_int, P, P, P, P, ctypes.c_int, POINTER(c_int64), POINTER(c_int32), c_void_p]),
     "nnhipStridedCopy": (ctypes.c_int, [P, P, c_float, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
     "nnhipTensorOpsLastTier": (ctypes.c_int, [POINTER(c_int64)]),
+    "nnhipCompare": (ctypes.c_int, [ctypes.c_int, P, P, P, c_double, c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, POINTER(c_int64),
+                                    POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "nnhipLogical": (ctypes.c_int, [ctypes.c_int, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, POINTER(c_int64), POINTER(c_int64),
+                                    POINTER(c_int64), c_void_p]),
+    "nnhipWhereForward": (ctypes.c_int, [P, P, ctypes.c_int, P, P, c_float, c_float, ctypes.c_int, POINTER(c_int64), POINTER(c_int64),
+                                         POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "nnhipWhereBackward": (ctypes.c_int, [P, P, P, P, ctypes.c_int, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                          POINTER(c_int64), c_void_p]),
+    "nnhipSliceForward": (ctypes.c_int, [P, P, c_int64, ctypes.c_int, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "nnhipSliceBackward": (ctypes.c_int, [P, P, ctypes.c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "nnhipStridedAssign": (ctypes.c_int, [P, c_int64, POINTER(c_int64), P, POINTER(c_int64), c_double, c_int64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, POINTER(c_int64), c_void_p]),
+    "nnhipIndexGather": (ctypes.c_int, [P, P, ctypes.c_int, POINTER(c_void_p), ctypes.c_int, ctypes.c_int, POINTER(c_int64), c_int64, c_int64,
+                                        c_int64, c_void_p]),
+    "nnhipIndexAssign": (ctypes.c_int, [P, P, c_double, c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, POINTER(c_void_p), ctypes.c_int,
+                                        ctypes.c_int, POINTER(c_int64), c_int64, c_int64, c_int64, c_void_p]),
+    "nnhipMaskedAssign": (ctypes.c_int, [P, P, P, c_double, c_int64, ctypes.c_int, ctypes.c_int, c_int64, c_int64, c_void_p]),
+    "nnhipArgminF32": (ctypes.c_int, [P, P, c_int64, c_int64, c_int64, c_void_p]),
     "nnhipCommUniqueId": (ctypes.c_int, [ctypes.c_char_p]),
     "nnhipCommInitRank": (ctypes.c_int, [POINTER(c_void_p), ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "nnhipCommDestroy": (ctypes.c_int, [c_void_p]),

@@ -7,8 +7,9 @@ Restates the contract of neunet/autograd.py that the accelerated layers rely on 
     in reverse                                                        (autograd.py:965-1002)
 The arithmetic core of the reference Tensor -- the broadcasting binary ops and their operators, the unary maps, the axis
 reductions, transpose / swapaxes / .T and matmul (autograd.py:96-531, 588-640, 810-893) -- runs on the device through
-tensor_ops.py (csrc/tensor_ops.hip); comparisons and logical ops, where, flip, __getitem__ / __setitem__ and integer
-tensors are not provided yet.
+tensor_ops.py (csrc/tensor_ops.hip); comparisons and logical ops, where, flip, __getitem__ / __setitem__ (autograd.py:642-808,
+895-923) run through tensor_index.py (csrc/tensor_index.hip) on float32, int32, int64 and bool tensors, and in NumPy on a CPU
+tensor.  Boolean-mask __getitem__ (a data-dependent shape) and comparisons between tensors of different dtypes are not provided.
 
 Device arrays: on device "cuda" `Tensor.data` is a torch.Tensor living in HBM (torch-ROCm plays the
 role CuPy plays in the reference: allocation + streams only); on "cpu" it is a numpy.ndarray and the
@@ -487,6 +488,81 @@ class Tensor:
         NaN); the backward is grad / self.  Device float32 only: one nnhipActivationForward launch (kind NNHIP_ACT_LOG)."""
         from .nn.experimental.activations import ACT_LOG, hip_activation
         return hip_activation(self, ACT_LOG, "log")
+
+    # ---- comparisons and logical ops (autograd.py:686-808): bool tensors off the tape --------------------------------------------------
+    # An operand that is neither a Tensor, a number nor an array-like gives NotImplemented, so `t == None` is False and `t in [None]`
+    # works.  There is no __bool__, as in the reference: compare tensors by identity (`is`) in host code.
+    def _compare(self, t, op):
+        from .tensor_index import compare
+        return compare(self, t, op)
+
+    def _logical(self, t, op):
+        from .tensor_index import logical
+        return logical(self, t, op)
+
+    def equal(self, t) -> "Tensor":
+        return self._compare(t, "equal")
+
+    def not_equal(self, t) -> "Tensor":
+        return self._compare(t, "not_equal")
+
+    def greater(self, t) -> "Tensor":
+        return self._compare(t, "greater")
+
+    def greater_equal(self, t) -> "Tensor":
+        return self._compare(t, "greater_equal")
+
+    def less(self, t) -> "Tensor":
+        return self._compare(t, "less")
+
+    def less_equal(self, t) -> "Tensor":
+        return self._compare(t, "less_equal")
+
+    def logical_and(self, t) -> "Tensor":
+        return self._logical(t, "logical_and")
+
+    def logical_or(self, t) -> "Tensor":
+        return self._logical(t, "logical_or")
+
+    def logical_not(self) -> "Tensor":
+        return self._logical(None, "logical_not")
+
+    __eq__ = equal
+    __ne__ = not_equal
+    __gt__ = greater
+    __ge__ = greater_equal
+    __lt__ = less
+    __le__ = less_equal
+    __and__ = logical_and
+    __or__ = logical_or
+    __invert__ = logical_not
+    __hash__ = object.__hash__      # defining __eq__ would otherwise make Tensors unhashable (parameter sets, tape bookkeeping)
+
+    # ---- where, flip, indexing (autograd.py:642-684, 895-923) --------------------------------------------------------------------------
+    def where(self, condition, t) -> "Tensor":
+        """np.where(condition, self, t): float32 out; the backward is a select (dSelf = condition ? g : 0), summed over broadcast axes."""
+        from .tensor_index import where
+        return where(condition, self, t)
+
+    def flip(self, axis=None) -> "Tensor":
+        from .tensor_index import flip
+        return flip(self, axis)
+
+    def __getitem__(self, index) -> "Tensor":
+        """A contiguous copy (basic keys; integer arrays on adjacent axes).  The backward ASSIGNS into zeros as the reference does:
+        for repeated indices the last occurrence in C order wins."""
+        from .tensor_index import getitem
+        return getitem(self, index)
+
+    def __setitem__(self, key, value):
+        from .tensor_index import setitem
+        setitem(self, key, value)
+
+    def contiguous(self) -> "Tensor":
+        return self
+
+    def __abs__(self) -> "Tensor":
+        return self.abs()
 
     def __repr__(self):
         return f"Tensor(shape={self.shape}, dtype={self.dtype}, device={self.device}, op={self.op})"

@@ -9,8 +9,8 @@ Three layers, top to bottom:
     (tests/test_tape_ops.py) and the GPU tests can aim a case at a tier;
   * the C entries nnhipBroadcastBinary*, nnhipReduceAxes*, nnhipStridedCopy (csrc/tensor_ops.hip) and nnhipGemmF32 for matmul.
 
-Device float32 only; a CPU tensor raises NotImplementedError (no CPU fallback).  Out of scope: comparisons and logical ops, where,
-flip, __getitem__ / __setitem__, integer tensors.
+Device float32 only; a CPU tensor raises NotImplementedError (no CPU fallback).  Comparisons and logical ops, where, flip,
+__getitem__ / __setitem__ and the integer / bool tensors they need live in tensor_index.py (csrc/tensor_index.hip).
 """
 from __future__ import annotations
 

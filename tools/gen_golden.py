@@ -1875,10 +1875,37 @@ def gen_conway():
     save("conway_steps", **arrs)
 
 
+def gen_tape_index():
+    """tape_index.npz: comparisons, logical ops, where, flip, __getitem__ / __setitem__ and six compositions (the notebooks' masked
+    scores, sinusoidal table, last-step logits, gathered log-probabilities, embedding lookup with repeated ids, a flipped sum of squares)
+    on the reference's tape.  The cases live in tests/index_ref.py (tape_index_cases) -- the tests run the same functions on
+    neunet_hip.  Per case the inputs, the output and, where the output is on the tape, an upstream gradient and the gradient of every
+    input that requires one ("<case>/in<i>", "/Y", "/dY", "/d<i>")."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import index_ref as IR
+    rng = np.random.default_rng(224)
+    arrs = {}
+    for tag, (specs, fn) in IR.tape_index_cases().items():
+        ins = [IR.draw(rng, s) for s in specs]
+        ts = [T(a.copy(), requires_grad=s[1] == "f", dtype=a.dtype) for a, s in zip(ins, specs)]
+        y = fn(neunet, "cpu", *ts)
+        arrs[f"{tag}/Y"] = np.asarray(y.data).copy()
+        for i, a in enumerate(ins):
+            arrs[f"{tag}/in{i}"] = a
+        if y.requires_grad:
+            dY = rng.standard_normal(np.shape(y.data)).astype(F32)
+            y.backward(dY)
+            arrs[f"{tag}/dY"] = dY
+            for i, (a, t, s) in enumerate(zip(ins, ts, specs)):
+                if s[1] == "f":
+                    arrs[f"{tag}/d{i}"] = np.asarray(t.grad, F32).reshape(a.shape)
+    save("tape_index", **arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
               gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules, gen_activations_losses,
-              gen_word2vec, gen_tape_ops, gen_conway]
+              gen_word2vec, gen_tape_ops, gen_conway, gen_tape_index]
 
 
 def generate_all(out_dir=None, quiet=False):

@@ -555,6 +555,112 @@ def main():
                   rounds=2, nbytes={"general tier": 4.0 * X4.numel(), "torch": 4.0 * X4.numel()})
         del X4
 
+    if "index" in only:
+        # The indexing half of the tape (csrc/tensor_index.hip): every entry beside the torch expression of the same result (written into
+        # a preallocated output where torch has an out= form, the bare expression otherwise: never an extra copy) and beside a plain
+        # stream of the same footprint (`stream`: the float4 stream tools/stream_roof.py measures, nnhipReLUForward, over as many bytes
+        # as the entry moves, half read and half written).
+        import ctypes
+
+        def i64(*v):
+            return (ctypes.c_int64 * max(len(v), 1))(*v)
+
+        def stream_of(nbytes):
+            """tools/stream_roof.py's 8 B / element stream over nbytes in all (half each way)."""
+            half = int(nbytes // 8)
+            s, d = torch.zeros(half, device=dev), torch.empty(half, device=dev)
+            return lambda: call("nnhipReLUForward", d, s, half, st)
+
+        n = 1 << 26
+        A, B, O = randn(n), randn(n), torch.empty(n, device=dev)
+        Ob = torch.empty(n, dtype=torch.bool, device=dev)
+        C = (A > 0)
+        sh, s1 = i64(n), i64(1)
+        alternate("compare 2^26", {"nnhipCompare": lambda: call("nnhipCompare", 2, Ob, A, B, 0.0, 0, 0, 0, 1, sh, s1, s1, st),
+                                   "torch": lambda: torch.gt(A, B, out=Ob), "stream": stream_of(9.0 * n)},
+                  rounds=3, nbytes={k: 9.0 * n for k in ("nnhipCompare", "torch", "stream")})
+        alternate("where 2^26", {"nnhipWhereForward": lambda: call("nnhipWhereForward", O, C, 3, A, B, 0.0, 0.0, 1, sh, s1, s1, s1, st),
+                                 "torch": lambda: torch.where(C, A, B, out=O), "stream": stream_of(13.0 * n)},
+                  rounds=3, nbytes={k: 13.0 * n for k in ("nnhipWhereForward", "torch", "stream")})
+        del A, B, O, Ob, C
+        # the notebook's masked scores: where(mask[:, None] == 0, -1e9, scores), scores [64,8,256,256], mask [64,1,256,256]
+        shp, ms = (64, 8, 256, 256), (64, 1, 256, 256)
+        S, G = randn(*shp), randn(*shp)
+        Mk = (torch.rand(*ms, device=dev, generator=g) < 0.2)
+        O, dS = torch.empty_like(S), torch.empty_like(S)
+        neg, zero = torch.tensor(-1e9, device=dev), torch.zeros((), device=dev)
+        ne = S.numel()
+        sh4, full4, sm4 = i64(*shp), i64(8 * 65536, 65536, 256, 1), i64(65536, 0, 256, 1)
+        alternate("where [64,8,256,256] mask [64,1,..]",
+                  {"fwd": lambda: call("nnhipWhereForward", O, Mk, 3, None, S, -1e9, 0.0, 4, sh4, sm4, None, full4, st),
+                   "torch fwd": lambda: torch.where(Mk, neg, S, out=O),
+                   "bwd": lambda: call("nnhipWhereBackward", None, dS, G, Mk, 3, 4, sh4, sm4, None, full4, st),
+                   "torch bwd": lambda: torch.where(Mk, zero, G, out=dS),
+                   "stream": stream_of(8.125 * ne)},
+                  rounds=3, nbytes={k: 8.125 * ne for k in ("fwd", "torch fwd", "bwd", "torch bwd", "stream")})
+        del S, G, Mk, O, dS
+        # x[:, -1], x[:, ::2] and flip(1) on [64, 256, 512]
+        Bx, Tx, Dx = 64, 256, 512
+        X = randn(Bx, Tx, Dx)
+        cs = (Tx * Dx, Dx, 1)
+        last, dlast = torch.empty(Bx, Dx, device=dev), randn(Bx, Dx)
+        half, dhalf = torch.empty(Bx, Tx // 2, Dx, device=dev), randn(Bx, Tx // 2, Dx)
+        FX, dX = torch.empty_like(X), torch.empty_like(X)
+        nx = X.numel()
+        alternate("x[:, -1] [64,256,512]",
+                  {"fwd": lambda: call("nnhipSliceForward", last, X, (Tx - 1) * Dx, 0, 2, i64(Bx, Dx), i64(cs[0], 1), st),
+                   "torch fwd": lambda: last.copy_(X[:, -1]),
+                   "bwd": lambda: call("nnhipSliceBackward", dX, dlast, 3, i64(Bx, Tx, Dx), i64(0, Tx - 1, 0), i64(1, 1, 1), i64(Bx, 1, Dx), st),
+                   "torch bwd": lambda: (dX.zero_(), dX[:, -1].copy_(dlast)),
+                   "stream bwd": stream_of(4.0 * nx)},
+                  rounds=3, nbytes={"fwd": 8.0 * Bx * Dx, "torch fwd": 8.0 * Bx * Dx, "bwd": 4.0 * nx, "torch bwd": 4.0 * nx, "stream bwd": 4.0 * nx})
+        alternate("x[:, ::2] [64,256,512]",
+                  {"fwd": lambda: call("nnhipSliceForward", half, X, 0, 0, 3, i64(Bx, Tx // 2, Dx), i64(cs[0], 2 * Dx, 1), st),
+                   "torch fwd": lambda: half.copy_(X[:, ::2]),
+                   "bwd": lambda: call("nnhipSliceBackward", dX, dhalf, 3, i64(Bx, Tx, Dx), i64(0, 0, 0), i64(1, 2, 1), i64(Bx, Tx // 2, Dx), st),
+                   "torch bwd": lambda: (dX.zero_(), dX[:, ::2].copy_(dhalf)),
+                   "stream fwd": stream_of(4.0 * nx), "stream bwd": stream_of(6.0 * nx)},
+                  rounds=3, nbytes={"fwd": 4.0 * nx, "torch fwd": 4.0 * nx, "bwd": 6.0 * nx, "torch bwd": 6.0 * nx, "stream fwd": 4.0 * nx,
+                                    "stream bwd": 6.0 * nx})
+        alternate("flip(1) [64,256,512]",
+                  {"fwd": lambda: call("nnhipSliceForward", FX, X, (Tx - 1) * Dx, 0, 3, i64(Bx, Tx, Dx), i64(cs[0], -Dx, 1), st),
+                   "torch": lambda: torch.flip(X, (1,)), "stream": stream_of(8.0 * nx)},
+                  rounds=3, nbytes={k: 8.0 * nx for k in ("fwd", "torch", "stream")})
+        del X, FX, dX, half, dhalf
+        # a row gather: 16384 ids from a 15000-row table of 512 floats, beside nnhipEmbeddingForward without pe
+        V, Dm, Ni = 15000, 512, 16384
+        W = randn(V, Dm)
+        ids = torch.randint(0, V, (Ni,), device=dev, dtype=torch.int32, generator=g)
+        out, dW, gO = torch.empty(Ni, Dm, device=dev), torch.empty(V, Dm, device=dev), randn(Ni, Dm)
+        p1 = (ctypes.c_void_p * 4)(ids.data_ptr(), 0, 0, 0)
+        gb = 8.0 * Ni * Dm
+        alternate("rows [15000,512][16384 ids]",
+                  {"nnhipIndexGather": lambda: call("nnhipIndexGather", out, W, 0, p1, 1, 1, i64(V), 1, Ni, Dm, st),
+                   "nnhipEmbeddingForward": lambda: call("nnhipEmbeddingForward", out, W, ids, None, Ni, Dm, Ni, V, 1.0, st),
+                   "torch": lambda: torch.index_select(W, 0, ids, out=out),
+                   "bwd nnhipIndexAssign": lambda: call("nnhipIndexAssign", dW, gO, 0.0, 0, 0, 0, 1, p1, 1, 1, i64(V), 1, Ni, Dm, st),
+                   "bwd nnhipEmbeddingBackward": lambda: call("nnhipEmbeddingBackward", dW, gO, ids, Ni, Dm, V, 1.0, st),
+                   "stream": stream_of(gb)},
+                  rounds=3, nbytes={"nnhipIndexGather": gb, "nnhipEmbeddingForward": gb, "torch": gb, "bwd nnhipIndexAssign": 8.0 * V * Dm,
+                                    "bwd nnhipEmbeddingBackward": 8.0 * V * Dm, "stream": gb})
+        del W, out, dW, gO
+        # the element gather logp[arange(N), y] on [16384, 15000], forward and backward (the backward writes all of dX)
+        Nr, Cc = 16384, 15000
+        L = randn(Nr, Cc)
+        ar = torch.arange(Nr, device=dev, dtype=torch.int64)
+        y = torch.randint(0, Cc, (Nr,), device=dev, dtype=torch.int64, generator=g)
+        pick, gp, dL = torch.empty(Nr, device=dev), randn(Nr), torch.empty_like(L)
+        p2 = (ctypes.c_void_p * 4)(ar.data_ptr(), y.data_ptr(), 0, 0)
+        nl = L.numel()
+        alternate("elements [16384,15000][arange, y]",
+                  {"fwd": lambda: call("nnhipIndexGather", pick, L, 0, p2, 2, 2, i64(Nr, Cc), 1, Nr, 1, st),
+                   "torch fwd": lambda: L[ar, y],
+                   "bwd": lambda: call("nnhipIndexAssign", dL, gp, 0.0, 0, 0, 0, 1, p2, 2, 2, i64(Nr, Cc), 1, Nr, 1, st),
+                   "torch bwd": lambda: (dL.zero_(), dL.index_put_((ar, y), gp)),
+                   "stream bwd": stream_of(4.0 * nl)},
+                  rounds=2, nbytes={"fwd": 12.0 * Nr, "torch fwd": 12.0 * Nr, "bwd": 4.0 * nl, "torch bwd": 4.0 * nl, "stream bwd": 4.0 * nl})
+        del L, dL
+
     if "logsoftmax" in only:
         # nnhipLogSoftmaxForward / Backward beside nnhipSoftmaxForward / Backward (csrc/rowops.hip): the same tiers and the same bytes
         for (rows, cols) in [(8192, 1024), (16384, 15000), (64, 50000)]:
