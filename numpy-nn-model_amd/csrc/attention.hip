@@ -982,7 +982,7 @@ static bool extra_active(const AttnExtra& x) { return x.mask_bits || x.drop_mask
 // Head dim 64 runs 2-wave blocks by default: B64 T256 H8 forward 78.8 -> 75.3 us, backward 242 -> 228 us; T = 1024 +-0 / -3 %.
 // NNHIP_ATTN_WAVES = 2 | 4 is the developer A/B switch.
 static int attn_waves() {
-    static const int w = []() { const char* e = getenv("NNHIP_ATTN_WAVES"); const int v = e ? atoi(e) : 2; return v == 4 ? 4 : 2; }();
+    static const int w = env_int("NNHIP_ATTN_WAVES", 2) == 4 ? 4 : 2;
     return w;
 }
 
@@ -992,7 +992,7 @@ static int attn_waves() {
 // second item's loop around them: forward only).  Taken when the halved grid still gives every CU two
 // blocks and the sequence has at most 8 row blocks (T = 1024: 16 blocks, -1 %).  *Tgrid: the T the grid macro should see.
 static int attn_pair(int64_t BH, int64_t T, int64_t head_dim, int causal, int64_t* Tgrid) {
-    static const int mode = []() { const char* e = getenv("NNHIP_ATTN_PAIR"); return e ? atoi(e) : -1; }();   // dev knob: 0 off, 1 always
+    static const int mode = env_int("NNHIP_ATTN_PAIR", -1);   // dev knob: 0 off, 1 always
     const int64_t bq = (head_dim == 64 && attn_waves() == 2) ? 64 : 128;
     const int64_t nblk = ceil_div(T, bq), pairs = (nblk + 1) / 2;
     bool on = causal && nblk >= 2 && nblk <= 8 && BH * pairs >= 512;

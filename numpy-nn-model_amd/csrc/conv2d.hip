@@ -10,25 +10,27 @@
 //             (terms exist only where the divisions are exact and in range)
 //   wgrad   : dW[co,(ci,r,s)] = sum_{b,ho,wo} dO[b,co,ho,wo] * X[b,ci,ho*sh-pu+r*dh, wo*sw-pl+s*dw];  db[co] = sum dO
 // At the C5 shapes (K = 9/72, Cout = 8/16) the work is HBM/latency bound, not MFMA bound.
-#include <stdlib.h>
+//
+// Layout: the reduces and their deferred queue; the direct kernels; the two small-channel weight-gradient kernels; then the host
+// side (from conv_quad_on()), which reads as the routes tests/conv_ref.py::route() restates:
+//   forward : conv_direct_forward() (quad or one thread per position) | conv_mfma_forward()
+//   dX      : conv_direct_dgrad()   (quad2, quad or one thread per position) | conv_mfma_dgrad()
+//   dW, db  : conv_small_wgrad()    (partials -> conv_mfma_wgrad_kernel where mfma_wgrad_plan() fits, else conv_direct_wgrad_kernel
+//             -> reduce; nnhipConv2dWeightGradPooled runs the same sequence) | conv_mfma_wgrad()
+//   fused   : conv_pool_forward()   (one thread per window | four lanes per window, with or without statistics)
+#include <type_traits>
 
 #include "conv_common.h"
 #include "deferred_queue.h"
 
 namespace nnhip {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// The MFMA implicit-GEMM kernels (any layer above 16 channels) live in conv_mfma.hip; this file holds the entry points, the
-// direct kernels of the small-channel 3x3 layers (C5) and the partial-sum reduces they share.
-
 // dW[m][n] = sum_c part[c][m][n] (n < Nw);  db[m] = sum_c part[c][m][Nw].  One wave per output element:
 // the 64 lanes stride over the chunks and meet in a shuffle reduction (fixed order: deterministic).
-__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ part,
-                                                                float* __restrict__ dW,
-                                                                float* __restrict__ db, int chunks,
-                                                                int Cout, int Nw, int ncols) {
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+// `block`: the block's number among those of this reduce.
+__device__ __forceinline__ void conv_wgrad_reduce_block(const float* __restrict__ part, float* __restrict__ dW, float* __restrict__ db,
+                                                        int chunks, int Cout, int Nw, int ncols, int block) {
+    const int idx = block * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int total = Cout * ncols;
     if (idx >= total) return;
@@ -43,6 +45,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
             db[m] = s;
         }
     }
+}
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dW,
+                                                                float* __restrict__ db, int chunks, int Cout, int Nw, int ncols) {
+    conv_wgrad_reduce_block(part, dW, db, chunks, Cout, Nw, ncols, blockIdx.x);
 }
 
 // ---- the reduces of several layers as one launch (deferred parameter gradients, common.h) ----------------------------------
@@ -64,31 +70,21 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_group_kernel(const Conv
     const int Nw = k == 0 ? grp.j[0].Nw : k == 1 ? grp.j[1].Nw : k == 2 ? grp.j[2].Nw : grp.j[3].Nw;
     const int ncols = k == 0 ? grp.j[0].ncols : k == 1 ? grp.j[1].ncols : k == 2 ? grp.j[2].ncols : grp.j[3].ncols;
     const int first = k == 0 ? 0 : k == 1 ? grp.start[1] : k == 2 ? grp.start[2] : grp.start[3];
-    const int idx = ((int)blockIdx.x - first) * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int total = Cout * ncols;
-    if (idx >= total) return;
-    const int m = idx / ncols, n = idx - m * ncols;
-    float s = 0.f;
-    for (int c = lane; c < chunks; c += 64) s += part[(int64_t)c * total + idx];
-    s = wave_sum(s);
-    if (lane == 0) {
-        if (n < Nw) {
-            if (dW) dW[(int64_t)m * Nw + n] = s;
-        } else if (db) {
-            db[m] = s;
-        }
-    }
+    conv_wgrad_reduce_block(part, dW, db, chunks, Cout, Nw, ncols, (int)blockIdx.x - first);
 }
 
+static int conv_reduce_blocks(const ConvReduceJob& j) { return (int)ceil_div((int64_t)j.Cout * j.ncols, 4); }   // one wave per output
+static int conv_reduce_launch(const ConvReduceJob& j, hipStream_t st) {
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)conv_reduce_blocks(j)), dim3(256), 0, st, j.part, j.dW, j.db, j.chunks, j.Cout,
+                       j.Nw, j.ncols);
+    NNHIP_LAUNCH_CHECK("conv_wgrad_reduce_kernel");
+    return 0;
+}
 static int conv_reduce_group_launch(const ConvReduceJob* q, int n, int, hipStream_t st) {
+    if (n == 1) return conv_reduce_launch(q[0], st);
     ConvReduceGroup grp;
-    const int blocks = group_starts<CRQ_MAX>(q, n, grp.j, grp.start, [](const ConvReduceJob& j) { return (int)ceil_div((int64_t)j.Cout * j.ncols, 4); });
-    if (n == 1)
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q[0].part, q[0].dW, q[0].db, q[0].chunks,
-                           q[0].Cout, q[0].Nw, q[0].ncols);
-    else
-        hipLaunchKernelGGL(conv_wgrad_reduce_group_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grp);
+    const int blocks = group_starts<CRQ_MAX>(q, n, grp.j, grp.start, conv_reduce_blocks);
+    hipLaunchKernelGGL(conv_wgrad_reduce_group_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grp);
     NNHIP_LAUNCH_CHECK("conv_wgrad_reduce_group_kernel");
     return 0;
 }
@@ -98,25 +94,20 @@ void conv_reduce_cleanup() { g_crq.cleanup(); }
 // Where a weight-gradient kernel writes its `floats` partials: the arena when its reduce can wait for the flush (*deferred),
 // else the shared workspace (reduce launched at once).  nullptr: out of memory.
 static float* conv_partials(size_t floats, hipStream_t st, bool* deferred, int* rc) {
-    static const bool on = []() { const char* e = getenv("NNHIP_CONV_DEFER_REDUCE"); return !e || atoi(e) != 0; }();
+    static const bool on = env_int("NNHIP_CONV_DEFER_REDUCE", 1) != 0;
     *rc = 0;
     float* p = on && wgrad_defer_on() ? g_crq.reserve(floats, 1, 0, st, floats + (floats >> 1), rc) : nullptr;
     *deferred = p != nullptr;
     return p || *rc ? p : static_cast<float*>(workspace(floats * sizeof(float)));
 }
-static int conv_reduce(const float* part, float* dW, float* db, int chunks, int Cout, int Nw, int ncols, hipStream_t st, bool deferred) {
-    if (deferred) {
-        g_crq.push(ConvReduceJob{part, dW, db, chunks, Cout, Nw, ncols});
-        return 0;
-    }
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)ceil_div((int64_t)Cout * ncols, 4)), dim3(256), 0, st, part, dW, db, chunks,
-                       Cout, Nw, ncols);
-    NNHIP_LAUNCH_CHECK("conv_wgrad_reduce_kernel");
+static int conv_reduce(const ConvReduceJob& j, hipStream_t st, bool deferred) {
+    if (!deferred) return conv_reduce_launch(j, st);
+    g_crq.push(j);
     return 0;
 }
 
 // =================================================================================================
-// Direct kernels for SMALL channel counts (Cin, Cout <= 16, kh*kw <= 25): the implicit GEMM above pads an 8- or
+// Direct kernels for SMALL channel counts (Cin, Cout <= 16, kh*kw <= 25): the implicit GEMM (conv_mfma.hip) pads an 8- or
 // 16-row problem to 32-row MFMA tiles and spends its time gathering (C5: dgrad 60 us, wgrad 38 us, fwd 29 us for
 // 58 MFLOP layers).  Here one thread owns one output (input) pixel and all CO (CI) channels of it in registers; the
 // weights sit in LDS laid out so that one ds_read_b128 hands a thread 4 channels' weights for the tap it is on (all
@@ -144,6 +135,15 @@ __device__ __forceinline__ void stage_to_lds(float* __restrict__ dst, const floa
             if (i < n) dst[i] = t[j];
         }
     }
+}
+
+// the 3x3 dgrad kernels' weights: Wl[(co*9 + tap) * CI + ci], zero for ci >= Cin
+template <int CI>
+__device__ __forceinline__ void stage_dgrad_weights_3x3(float* __restrict__ Wl, const float* __restrict__ Wt, const ConvGeom& g) {
+    stage_to_lds(Wl, Wt, g.Cout * 9 * CI, threadIdx.x, [&](int i) -> int64_t {
+        const int ci = i % CI, k = i / CI, co = k / 9, rs = k - co * 9;
+        return ci < g.Cin ? ((int64_t)co * g.Cin + ci) * 9 + rs : -1;
+    });
 }
 
 constexpr unsigned CD_OOB = 0xFFFFFFF0u;                   // a byte offset no descriptor below covers
@@ -496,10 +496,7 @@ __global__ __launch_bounds__(256) void conv_direct_dgrad_quad_kernel(const float
                                                                      float* __restrict__ dX, const ConvGeom g) {
     constexpr int CPL = CD_MAXC / 4;
     __shared__ __attribute__((aligned(16))) float Wl[CD_MAXC * 9 * CI];
-    stage_to_lds(Wl, Wt, g.Cout * 9 * CI, threadIdx.x, [&](int i) -> int64_t {
-        const int ci = i % CI, k = i / CI, co = k / 9, rs = k - co * 9;
-        return ci < g.Cin ? ((int64_t)co * g.Cin + ci) * 9 + rs : -1;
-    });
+    stage_dgrad_weights_3x3<CI>(Wl, Wt, g);
     __syncthreads();
     const int64_t HW = (int64_t)g.H * g.W, N = (int64_t)g.B * HW;
     const int HWo = g.Ho * g.Wo;
@@ -583,10 +580,7 @@ __global__ __launch_bounds__(256) void conv_direct_dgrad_quad2_kernel(const floa
                                                                       float* __restrict__ dX, const ConvGeom g) {
     constexpr int CPL = CD_MAXC / 4;
     __shared__ __attribute__((aligned(16))) float Wl[CD_MAXC * 9 * CI];
-    stage_to_lds(Wl, Wt, g.Cout * 9 * CI, threadIdx.x, [&](int i) -> int64_t {
-        const int ci = i % CI, k = i / CI, co = k / 9, rs = k - co * 9;
-        return ci < g.Cin ? ((int64_t)co * g.Cin + ci) * 9 + rs : -1;
-    });
+    stage_dgrad_weights_3x3<CI>(Wl, Wt, g);
     __syncthreads();
     const int Hb = (g.H + 1) >> 1, Wb = (g.W + 1) >> 1, HWb = Hb * Wb;
     const int64_t N = (int64_t)g.B * HWb, HW = (int64_t)g.H * g.W;
@@ -793,7 +787,7 @@ __global__ __launch_bounds__(256) void conv_pool_fwd_quad_kernel(const float* __
 // loaded once and used for every co, dO[co][p] a broadcast read shared by the CIP threads of the slice.  The slices lie
 // along the lanes, so the per-image partial sums meet in a shuffle tree + one LDS hop; per-block partials go to
 // conv_wgrad_reduce_kernel.  (Thread <-> output element with a serial loop over the pixels was tried first: 1168 outputs
-// x 196 pixels per image left most lanes idle, 70-88 us; the MFMA split-K wgrad above takes 38 us at C5 -- it gathers
+// x 196 pixels per image left most lanes idle, 70-88 us; the MFMA split-K wgrad of conv_mfma.hip takes 38 us at C5 -- it gathers
 // every X element 9 times.)
 template <int CO, int CIP>
 __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(const float* __restrict__ X, const float* __restrict__ dO,
@@ -1059,9 +1053,9 @@ __global__ __launch_bounds__(256) void conv_mfma_wgrad_kernel(const float* __res
     }
 }
 
-template <int NT, bool POOL = false>
+template <int NT, bool POOL>
 static int launch_mfma_wgrad(const float* X, const float* dO, float* part, const ConvGeom& g, int ncols, int blocks, size_t lds,
-                             hipStream_t st, const PoolGrad pg = PoolGrad{}) {
+                             hipStream_t st, const PoolGrad& pg) {
     auto kern = conv_mfma_wgrad_kernel<NT, POOL>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1075,11 +1069,11 @@ static int launch_mfma_wgrad(const float* X, const float* dO, float* part, const
 }
 
 static bool conv_quad_on() {      // NNHIP_CONV_QUAD=0: the one-thread-per-position kernels everywhere (A/B switch)
-    static const bool on = []() { const char* e = getenv("NNHIP_CONV_QUAD"); return !e || atoi(e) != 0; }();
+    static const bool on = env_int("NNHIP_CONV_QUAD", 1) != 0;
     return on;
 }
 static bool conv_direct_ok(const ConvGeom& g) {
-    static const bool off = []() { const char* e = getenv("NNHIP_CONV_DIRECT"); return e && atoi(e) == 0; }();
+    static const bool off = env_int("NNHIP_CONV_DIRECT", 1) == 0;
     // (both activation tensors are addressed with 32-bit byte offsets below CD_OOB)
     const int64_t lim = (int64_t)1 << 29;
     return !off && g.Cin <= CD_MAXC && g.Cout <= CD_MAXC && g.kh * g.kw <= CD_MAXTAPS && (int64_t)g.B * g.Cin * g.H * g.W < lim &&
@@ -1105,56 +1099,106 @@ static int make_geom(const nnhipConv2dDesc* d, ConvGeom& g) {
     return 0;
 }
 
+// A kernel's channel-width instantiation: f(ic<W>) for the smallest W of LO, 2 LO, ..., HI with c <= W (HI takes everything above).
+// with_width<8, 16>(g.Cout, [&](auto co) { launch kernel<co()> }) launches <8> or <16>.
+template <int V>
+constexpr std::integral_constant<int, V> ic{};
+template <int LO, int HI, typename F>
+static void with_width(int c, F f) {
+    if constexpr (LO < HI) {
+        if (c > LO) return with_width<2 * LO, HI>(c, f);
+    }
+    f(ic<LO>);
+}
+
 }  // namespace nnhip
 
 using namespace nnhip;
 
-extern "C" int nnhipConv2dForward(const float* X, const float* W, const float* bias, float* O,
-                                  const nnhipConv2dDesc* d, nnhipStream_t s) {
+// ---- forward -----------------------------------------------------------------------------------------------------------------
+static int conv_direct_forward(const float* X, const float* W, const float* bias, float* O, const ConvGeom& g, hipStream_t st) {
+    const int64_t N = (int64_t)g.B * g.Ho * g.Wo;
+    // under two blocks per CU and a reduction worth splitting: four lanes per position
+    if (conv_quad_on() && g.kh == 3 && g.kw == 3 && N <= 512 * 256 && g.Cin >= 4 && g.Cout > 4) {
+        const dim3 grid((unsigned)ceil_div(4 * N, 256));
+        with_width<8, 16>(g.Cout, [&](auto co) { hipLaunchKernelGGL(conv_direct_fwd_quad_kernel<co()>, grid, dim3(256), 0, st, W, X, bias, O, g); });
+        NNHIP_LAUNCH_CHECK("conv_direct_fwd_quad_kernel");
+        return 0;
+    }
+    const dim3 grid((unsigned)ceil_div(N, 256));
+    with_width<4, 16>(g.Cout, [&](auto co) { hipLaunchKernelGGL(conv_direct_fwd_kernel<co()>, grid, dim3(256), 0, st, W, X, bias, O, g); });
+    NNHIP_LAUNCH_CHECK("conv_direct_fwd_kernel");
+    return 0;
+}
+
+extern "C" int nnhipConv2dForward(const float* X, const float* W, const float* bias, float* O, const nnhipConv2dDesc* d, nnhipStream_t s) {
     ConvGeom g;
     if (int rc = make_geom(d, g)) return rc;
     if (g.B == 0) return 0;
     NNHIP_CHECK_ARG(X && W && O, NNHIP_EINVAL, "nnhipConv2dForward: null pointer");
-    const int64_t N = (int64_t)g.B * g.Ho * g.Wo;
-    if (conv_direct_ok(g)) {
-        const dim3 dgrid((unsigned)ceil_div(N, 256));
-        // under two blocks per CU and a reduction worth splitting: four lanes per position (conv_direct_fwd_quad_kernel)
-        if (conv_quad_on() && g.kh == 3 && g.kw == 3 && N <= 512 * 256 && g.Cin >= 4 && g.Cout > 4) {
-            const dim3 qgrid((unsigned)ceil_div(4 * N, 256));
-            if (g.Cout <= 8) hipLaunchKernelGGL(conv_direct_fwd_quad_kernel<8>, qgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, O, g);
-            else hipLaunchKernelGGL(conv_direct_fwd_quad_kernel<16>, qgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, O, g);
-            NNHIP_LAUNCH_CHECK("conv_direct_fwd_quad_kernel");
-            return 0;
-        }
-        if (g.Cout <= 4) hipLaunchKernelGGL(conv_direct_fwd_kernel<4>, dgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, O, g);
-        else if (g.Cout <= 8) hipLaunchKernelGGL(conv_direct_fwd_kernel<8>, dgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, O, g);
-        else hipLaunchKernelGGL(conv_direct_fwd_kernel<16>, dgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, O, g);
-        NNHIP_LAUNCH_CHECK("conv_direct_fwd_kernel");
-        return 0;
-    }
-    return conv_mfma_forward(X, W, bias, O, g, (hipStream_t)s);
+    return conv_direct_ok(g) ? conv_direct_forward(X, W, bias, O, g, (hipStream_t)s) : conv_mfma_forward(X, W, bias, O, g, (hipStream_t)s);
 }
 
-// the LDS plan of conv_mfma_wgrad_kernel for geometry g: true iff that kernel can run it
-static bool mfma_wgrad_plan(const ConvGeom& g, int& ncols, int& nt, size_t& m_lds) {
-    static const bool mfma_on = []() { const char* e = getenv("NNHIP_CONV_WGRAD_MFMA"); return !e || atoi(e) != 0; }();
-    if (!mfma_on || !conv_direct_ok(g) || g.kh != 3 || g.kw != 3) return false;
-    ncols = g.Cin * 9 + 1;
-    nt = (ncols + 15) / 16;
-    const int Hp = (g.Ho - 1) * g.sh + 2 * g.dh + 1, Wp = (g.Wo - 1) * g.sw + 2 * g.dw + 1;
-    const int Lg = 4 * ((g.Ho * g.Wo + 3) / 4);
-    const int nt_inst = nt <= 3 ? nt : nt <= 5 ? 5 : 10;
-    m_lds = ((size_t)g.Cin * Hp * Wp + 4 + (size_t)g.Cout * Lg) * sizeof(float);
+// ---- the small-channel weight gradient: per-block partials, conv_mfma_wgrad_kernel or conv_direct_wgrad_kernel, the reduce ---------
+// The LDS plan of conv_mfma_wgrad_kernel for geometry g.  nt == 0: that kernel cannot run it (or NNHIP_CONV_WGRAD_MFMA=0).
+struct MfmaWgradPlan { int ncols, nt; size_t lds; };   // Cin * 9 weight columns + the db column; 16-column tiles; bytes
+static MfmaWgradPlan mfma_wgrad_plan(const ConvGeom& g) {
+    static const bool mfma_on = env_int("NNHIP_CONV_WGRAD_MFMA", 1) != 0;
+    MfmaWgradPlan p{g.Cin * 9 + 1, 0, 0};
+    if (!mfma_on || !conv_direct_ok(g) || g.kh != 3 || g.kw != 3) return p;
+    const int nt = (p.ncols + 15) / 16;
+    const int Hp = (g.Ho - 1) * g.sh + 2 * g.dh + 1, Wp = (g.Wo - 1) * g.sw + 2 * g.dw + 1;   // the padded image
+    const int Lg = 4 * ((g.Ho * g.Wo + 3) / 4);                                              // a dO row, zero-padded to whole 4-pixel steps
+    const int nt_inst = nt <= 3 ? nt : nt <= 5 ? 5 : 10;   // the instantiation that will run (its LDS meeting area is 16*NT wide)
+    p.lds = ((size_t)g.Cin * Hp * Wp + 4 + (size_t)g.Cout * Lg) * sizeof(float);
     const size_t m_red = (size_t)4 * 16 * 16 * nt_inst * sizeof(float);
-    if (m_lds < m_red) m_lds = m_red;
-    return nt <= 10 && m_lds <= 60 * 1024;
+    if (p.lds < m_red) p.lds = m_red;
+    if (nt <= 10 && p.lds <= 60 * 1024) p.nt = nt;
+    return p;
 }
+// the NT instantiation for the plan; pg: the pooled variant (dO built in LDS from the pool's gradient)
+static int launch_mfma_wgrad_plan(const float* X, const float* dO, const PoolGrad* pg, float* part, const ConvGeom& g,
+                                  const MfmaWgradPlan& p, int blocks, hipStream_t st) {
+    auto launch = [&](auto nt) {
+        return pg ? launch_mfma_wgrad<nt(), true>(X, nullptr, part, g, p.ncols, blocks, p.lds, st, *pg)
+                  : launch_mfma_wgrad<nt(), false>(X, dO, part, g, p.ncols, blocks, p.lds, st, PoolGrad{});
+    };
+    return p.nt <= 1 ? launch(ic<1>) : p.nt <= 2 ? launch(ic<2>) : p.nt <= 3 ? launch(ic<3>) : p.nt <= 5 ? launch(ic<5>) : launch(ic<10>);
+}
+// conv_direct_wgrad_kernel<CO = 8|16, CIP = 1|2|4|8|16>; lds: the image and its dO (the caller's wg_lds), at least the meeting area
+static int launch_direct_wgrad_width(const float* X, const float* dO, float* part, const ConvGeom& g, int ncols, int blocks, size_t lds,
+                                     hipStream_t st) {
+    int rc = 0;
+    with_width<8, 16>(g.Cout, [&](auto co) {
+        with_width<1, 16>(g.Cin, [&](auto cip) {
+            const size_t red = (size_t)4 * co() * (cip() * 9 + 1) * sizeof(float);
+            rc = launch_direct_wgrad<co(), cip()>(X, dO, part, g, ncols, blocks, lds < red ? red : lds, st);
+        });
+    });
+    return rc;
+}
+// Reserve blocks x [Cout][ncols] partials (the arena, with the reduce queued, while parameter gradients are deferred; else the shared
+// workspace, with the reduce behind the kernel), launch the MFMA kernel where the plan says it runs, else the direct kernel (dO given,
+// direct_lds its LDS bytes), reduce.  `who`: the entry point, for the out-of-memory message.
+static int conv_small_wgrad(const char* who, const float* X, const float* dO, const PoolGrad* pg, const MfmaWgradPlan& plan, size_t direct_lds,
+                            float* dW, float* db, const ConvGeom& g, hipStream_t st) {
+    const int blocks = g.B < 512 ? g.B : 512;
+    bool deferred;
+    int rc;
+    float* part = conv_partials((size_t)blocks * g.Cout * plan.ncols, st, &deferred, &rc);
+    if (rc) return rc;
+    NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "%s: workspace allocation failed", who);
+    rc = plan.nt ? launch_mfma_wgrad_plan(X, dO, pg, part, g, plan, blocks, st)
+                 : launch_direct_wgrad_width(X, dO, part, g, plan.ncols, blocks, direct_lds, st);
+    if (rc) return rc;
+    return conv_reduce(ConvReduceJob{part, dW, db, blocks, g.Cout, g.Cin * 9, plan.ncols}, st, deferred);
+}
+
 static bool pooled_wgrad_ok(const ConvGeom& g, const nnhipPool2dDesc* pd) {
-    static const bool on = []() { const char* e = getenv("NNHIP_CONV_POOLED_WGRAD"); return !e || atoi(e) != 0; }();
-    int ncols, nt; size_t lds;
+    static const bool on = env_int("NNHIP_CONV_POOLED_WGRAD", 1) != 0;
     return on && pd && pd->kh == pd->sh && pd->kw == pd->sw && pd->pu + pd->pd + pd->pl + pd->pr == 0 && pd->dh <= 1 && pd->dw <= 1 &&
            pd->kh >= 1 && pd->kw >= 1 && pd->kh * pd->kw <= 16 && pd->B == g.B && pd->C == g.Cout && pd->H == g.Ho && pd->W == g.Wo &&
-           g.Ho % pd->kh == 0 && g.Wo % pd->kw == 0 && mfma_wgrad_plan(g, ncols, nt, lds);
+           g.Ho % pd->kh == 0 && g.Wo % pd->kw == 0 && mfma_wgrad_plan(g).nt > 0;
 }
 
 extern "C" int nnhipConv2dWeightGradPooledOk(const nnhipConv2dDesc* d, const nnhipPool2dDesc* pd) {
@@ -1172,25 +1216,8 @@ extern "C" int nnhipConv2dWeightGradPooled(const float* X, const float* dP, cons
     NNHIP_CHECK_ARG(X && dP && argmax && (dW || db), NNHIP_EINVAL, "nnhipConv2dWeightGradPooled: null pointer");
     NNHIP_CHECK_ARG(pooled_wgrad_ok(g, pd), NNHIP_EINVAL,
                     "nnhipConv2dWeightGradPooled: unsupported geometry (ask nnhipConv2dWeightGradPooledOk first)");
-    hipStream_t st = (hipStream_t)s;
-    int ncols, nt; size_t m_lds;
-    mfma_wgrad_plan(g, ncols, nt, m_lds);
-    const int Nw = g.Cin * 9, total = g.Cout * ncols, blocks = g.B < 512 ? g.B : 512;
-    bool deferred;
-    int frc;
-    float* part = conv_partials((size_t)blocks * total, st, &deferred, &frc);
-    if (frc) return frc;
-    NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipConv2dWeightGradPooled: workspace allocation failed");
-    PoolGrad pg;
-    pg.dP = dP; pg.arg = argmax; pg.P = pooled; pg.alpha = alpha;
-    pg.Hq = g.Ho / (int)pd->kh; pg.Wq = g.Wo / (int)pd->kw; pg.kh = (int)pd->kh; pg.kw = (int)pd->kw;
-    int rc = nt <= 1 ? launch_mfma_wgrad<1, true>(X, nullptr, part, g, ncols, blocks, m_lds, st, pg)
-           : nt <= 2 ? launch_mfma_wgrad<2, true>(X, nullptr, part, g, ncols, blocks, m_lds, st, pg)
-           : nt <= 3 ? launch_mfma_wgrad<3, true>(X, nullptr, part, g, ncols, blocks, m_lds, st, pg)
-           : nt <= 5 ? launch_mfma_wgrad<5, true>(X, nullptr, part, g, ncols, blocks, m_lds, st, pg)
-                     : launch_mfma_wgrad<10, true>(X, nullptr, part, g, ncols, blocks, m_lds, st, pg);
-    if (rc) return rc;
-    return conv_reduce(part, dW, db, blocks, g.Cout, Nw, ncols, st, deferred);
+    const PoolGrad pg{dP, argmax, pooled, alpha, g.Ho / (int)pd->kh, g.Wo / (int)pd->kw, (int)pd->kh, (int)pd->kw};
+    return conv_small_wgrad("nnhipConv2dWeightGradPooled", X, nullptr, &pg, mfma_wgrad_plan(g), 0, dW, db, g, (hipStream_t)s);   // (the plan runs: pooled_wgrad_ok)
 }
 
 // one thread per window (conv_pool_fwd_kernel): few input channels, and windows enough to make a grid
@@ -1203,7 +1230,7 @@ static bool conv_pool_quad_ok(const ConvGeom& g) {
            g.dw == 1;
 }
 static bool conv_pool_fwd_ok(const ConvGeom& g, const nnhipPool2dDesc* pd) {
-    static const bool on = []() { const char* e = getenv("NNHIP_CONV_POOL_FWD"); return !e || atoi(e) != 0; }();
+    static const bool on = env_int("NNHIP_CONV_POOL_FWD", 1) != 0;
     // one thread per window: worth it while the windows still make a grid (the second C5 layer's 49 blocks do not)
     if (!(on && pd && pd->kh == 2 && pd->kw == 2 && pd->sh == 2 && pd->sw == 2 && pd->pu + pd->pd + pd->pl + pd->pr == 0 && pd->dh <= 1 &&
           pd->dw <= 1 && pd->B == g.B && pd->C == g.Cout && pd->H == g.Ho && pd->W == g.Wo && g.Ho % 2 == 0 && g.Wo % 2 == 0 &&
@@ -1225,8 +1252,32 @@ extern "C" int nnhipConv2dLeakyMaxPoolStatsBlocks(const nnhipConv2dDesc* d, cons
     const int64_t N = (int64_t)g.B * (g.Ho / 2) * (g.Wo / 2);
     return (N % 64 == 0 && N / 64 <= 65535) ? (int)(N / 64) : 0;
 }
+// stats: null, or where the four-lanes-per-window kernel leaves the partial batch statistics of P
 static int conv_pool_forward(const float* X, const float* W, const float* bias, float alpha, float* P, int32_t* argmax,
-                             const nnhipConv2dDesc* d, const nnhipPool2dDesc* pd, float* stats, nnhipStream_t s);
+                             const nnhipConv2dDesc* d, const nnhipPool2dDesc* pd, float* stats, nnhipStream_t s) {
+    ConvGeom g;
+    if (int rc = make_geom(d, g)) return rc;
+    if (g.B == 0) return 0;
+    NNHIP_CHECK_ARG(X && W && P && argmax, NNHIP_EINVAL, "nnhipConv2dLeakyMaxPoolForward: null pointer");
+    NNHIP_CHECK_ARG(alpha > 0.f, NNHIP_EINVAL, "nnhipConv2dLeakyMaxPoolForward: alpha must be > 0 (1 = no activation)");
+    NNHIP_CHECK_ARG(conv_pool_fwd_ok(g, pd), NNHIP_EINVAL,
+                    "nnhipConv2dLeakyMaxPoolForward: unsupported geometry (ask nnhipConv2dLeakyMaxPoolForwardOk first)");
+    hipStream_t st = (hipStream_t)s;
+    const int64_t N = (int64_t)g.B * (g.Ho / 2) * (g.Wo / 2);                 // windows
+    if (conv_pool_window_ok(g)) {                                             // one thread per window
+        const dim3 grid((unsigned)ceil_div(N, 256));
+        with_width<8, 16>(g.Cout, [&](auto co) { hipLaunchKernelGGL(conv_pool_fwd_kernel<co()>, grid, dim3(256), 0, st, W, X, bias, P, argmax, g, alpha); });
+        NNHIP_LAUNCH_CHECK("conv_pool_fwd_kernel");
+        return 0;
+    }
+    const dim3 grid((unsigned)ceil_div(4 * N, 256));                          // four lanes per window, each all four positions
+    with_width<8, 16>(g.Cout, [&](auto co) {
+        if (stats) hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<co(), true>), grid, dim3(256), 0, st, W, X, bias, P, argmax, g, alpha, stats);
+        else hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<co(), false>), grid, dim3(256), 0, st, W, X, bias, P, argmax, g, alpha, nullptr);
+    });
+    NNHIP_LAUNCH_CHECK("conv_pool_fwd_quad_kernel");
+    return 0;
+}
 extern "C" int nnhipConv2dLeakyMaxPoolForward(const float* X, const float* W, const float* bias, float alpha, float* P, int32_t* argmax,
                                               const nnhipConv2dDesc* d, const nnhipPool2dDesc* pd, nnhipStream_t s) {
     return conv_pool_forward(X, W, bias, alpha, P, argmax, d, pd, nullptr, s);
@@ -1240,107 +1291,45 @@ extern "C" int nnhipConv2dLeakyMaxPoolForwardStats(const float* X, const float* 
                     "nnhipConv2dLeakyMaxPoolForwardStats: no statistics variant for this geometry (ask nnhipConv2dLeakyMaxPoolStatsBlocks)");
     return conv_pool_forward(X, W, bias, alpha, P, argmax, d, pd, stats, s);
 }
-static int conv_pool_forward(const float* X, const float* W, const float* bias, float alpha, float* P, int32_t* argmax,
-                             const nnhipConv2dDesc* d, const nnhipPool2dDesc* pd, float* stats, nnhipStream_t s) {
-    ConvGeom g;
-    if (int rc = make_geom(d, g)) return rc;
-    if (g.B == 0) return 0;
-    NNHIP_CHECK_ARG(X && W && P && argmax, NNHIP_EINVAL, "nnhipConv2dLeakyMaxPoolForward: null pointer");
-    NNHIP_CHECK_ARG(alpha > 0.f, NNHIP_EINVAL, "nnhipConv2dLeakyMaxPoolForward: alpha must be > 0 (1 = no activation)");
-    NNHIP_CHECK_ARG(conv_pool_fwd_ok(g, pd), NNHIP_EINVAL,
-                    "nnhipConv2dLeakyMaxPoolForward: unsupported geometry (ask nnhipConv2dLeakyMaxPoolForwardOk first)");
-    if (!conv_pool_window_ok(g)) {                           // four lanes per window, each all four positions
-        const dim3 wgrid((unsigned)ceil_div(4 * (int64_t)g.B * (g.Ho / 2) * (g.Wo / 2), 256));
-        if (stats) {
-            if (g.Cout <= 8) hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<8, true>), wgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha, stats);
-            else hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<16, true>), wgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha, stats);
-        } else if (g.Cout <= 8) hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<8, false>), wgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha, nullptr);
-        else hipLaunchKernelGGL((conv_pool_fwd_quad_kernel<16, false>), wgrid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha, nullptr);
-        NNHIP_LAUNCH_CHECK("conv_pool_fwd_quad_kernel");
+
+// ---- backward ----------------------------------------------------------------------------------------------------------------
+static int conv_direct_dgrad(const float* W, const float* dO, float* dX, const ConvGeom& g, hipStream_t st) {
+    const int64_t N = (int64_t)g.B * g.H * g.W;
+    if (conv_quad_on() && g.kh == 3 && g.kw == 3 && N <= 512 * 256 && g.Cout >= 4 && g.Cin > 2 && g.Cin <= 8) {
+        static const bool quad2 = env_int("NNHIP_CONV_DGRAD_QUAD2", 1) != 0;
+        if (quad2 && g.sh == 1 && g.sw == 1 && g.dh == 1 && g.dw == 1) {      // 2x2 positions per quad of lanes
+            const dim3 grid((unsigned)ceil_div(4 * (int64_t)g.B * ((g.H + 1) / 2) * ((g.W + 1) / 2), 256));
+            with_width<4, 8>(g.Cin, [&](auto ci) { hipLaunchKernelGGL(conv_direct_dgrad_quad2_kernel<ci()>, grid, dim3(256), 0, st, W, dO, dX, g); });
+            NNHIP_LAUNCH_CHECK("conv_direct_dgrad_quad2_kernel");
+            return 0;
+        }
+        const dim3 grid((unsigned)ceil_div(4 * N, 256));                      // one position per quad of lanes
+        with_width<4, 8>(g.Cin, [&](auto ci) { hipLaunchKernelGGL(conv_direct_dgrad_quad_kernel<ci()>, grid, dim3(256), 0, st, W, dO, dX, g); });
+        NNHIP_LAUNCH_CHECK("conv_direct_dgrad_quad_kernel");
         return 0;
     }
-    const int64_t N = (int64_t)g.B * (g.Ho / 2) * (g.Wo / 2);
     const dim3 grid((unsigned)ceil_div(N, 256));
-    if (g.Cout <= 8) hipLaunchKernelGGL(conv_pool_fwd_kernel<8>, grid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha);
-    else hipLaunchKernelGGL(conv_pool_fwd_kernel<16>, grid, dim3(256), 0, (hipStream_t)s, W, X, bias, P, argmax, g, alpha);
-    NNHIP_LAUNCH_CHECK("conv_pool_fwd_kernel");
+    with_width<4, 16>(g.Cin, [&](auto ci) { hipLaunchKernelGGL(conv_direct_dgrad_kernel<ci()>, grid, dim3(256), 0, st, W, dO, dX, g); });
+    NNHIP_LAUNCH_CHECK("conv_direct_dgrad_kernel");
     return 0;
 }
 
-extern "C" int nnhipConv2dBackward(const float* X, const float* W, const float* dO, float* dX, float* dW,
-                                   float* db, const nnhipConv2dDesc* d, nnhipStream_t s) {
+extern "C" int nnhipConv2dBackward(const float* X, const float* W, const float* dO, float* dX, float* dW, float* db,
+                                   const nnhipConv2dDesc* d, nnhipStream_t s) {
     ConvGeom g;
     if (int rc = make_geom(d, g)) return rc;
     if (g.B == 0) return 0;
     NNHIP_CHECK_ARG(X && W && dO, NNHIP_EINVAL, "nnhipConv2dBackward: null pointer");
     hipStream_t st = (hipStream_t)s;
     const bool direct = conv_direct_ok(g);
-    if (dX && direct) {
-        const dim3 dgrid((unsigned)ceil_div((int64_t)g.B * g.H * g.W, 256));
-        const int64_t Nd = (int64_t)g.B * g.H * g.W;
-        if (conv_quad_on() && g.kh == 3 && g.kw == 3 && Nd <= 512 * 256 && g.Cout >= 4 && g.Cin > 2 && g.Cin <= 8) {
-            static const bool quad2 = []() { const char* e = getenv("NNHIP_CONV_DGRAD_QUAD2"); return !e || atoi(e) != 0; }();
-            if (quad2 && g.sh == 1 && g.sw == 1 && g.dh == 1 && g.dw == 1) {      // 2x2 positions per quad of lanes
-                const dim3 bgrid((unsigned)ceil_div(4 * (int64_t)g.B * ((g.H + 1) / 2) * ((g.W + 1) / 2), 256));
-                if (g.Cin <= 4) hipLaunchKernelGGL(conv_direct_dgrad_quad2_kernel<4>, bgrid, dim3(256), 0, st, W, dO, dX, g);
-                else hipLaunchKernelGGL(conv_direct_dgrad_quad2_kernel<8>, bgrid, dim3(256), 0, st, W, dO, dX, g);
-                NNHIP_LAUNCH_CHECK("conv_direct_dgrad_quad2_kernel");
-            } else {
-            const dim3 qgrid((unsigned)ceil_div(4 * Nd, 256));
-            if (g.Cin <= 4) hipLaunchKernelGGL(conv_direct_dgrad_quad_kernel<4>, qgrid, dim3(256), 0, st, W, dO, dX, g);
-            else hipLaunchKernelGGL(conv_direct_dgrad_quad_kernel<8>, qgrid, dim3(256), 0, st, W, dO, dX, g);
-            NNHIP_LAUNCH_CHECK("conv_direct_dgrad_quad_kernel");
-            }
-        } else
-        if (g.Cin <= 4) hipLaunchKernelGGL(conv_direct_dgrad_kernel<4>, dgrid, dim3(256), 0, st, W, dO, dX, g);
-        else if (g.Cin <= 8) hipLaunchKernelGGL(conv_direct_dgrad_kernel<8>, dgrid, dim3(256), 0, st, W, dO, dX, g);
-        else hipLaunchKernelGGL(conv_direct_dgrad_kernel<16>, dgrid, dim3(256), 0, st, W, dO, dX, g);
-        NNHIP_LAUNCH_CHECK("conv_direct_dgrad_kernel");
-    } else if (dX) {
-        if (int rc = conv_mfma_dgrad(dO, W, dX, g, st)) return rc;
+    if (dX) {
+        if (int rc = direct ? conv_direct_dgrad(W, dO, dX, g, st) : conv_mfma_dgrad(dO, W, dX, g, st)) return rc;
     }
-    size_t wg_lds = ((size_t)g.Cin * g.H * g.W + (size_t)g.Cout * g.Ho * g.Wo) * sizeof(float);
-    if ((dW || db) && direct && g.kh == 3 && g.kw == 3 && wg_lds <= 60 * 1024) {
-        const int Nw = g.Cin * 9, ncols = Nw + 1, total = g.Cout * ncols;
-        const int blocks = g.B < 512 ? g.B : 512;
-        bool deferred;
-        int frc;
-        float* part = conv_partials((size_t)blocks * total, st, &deferred, &frc);     // arena (reduce queued) or shared workspace
-        if (frc) return frc;
-        NNHIP_CHECK_ARG(part != nullptr, NNHIP_ENOMEM, "nnhipConv2dBackward: workspace allocation failed");
-        // the 16x16x4-MFMA kernel when its padded image + zero-padded dO fit LDS (NNHIP_CONV_WGRAD_MFMA=0: the direct kernel)
-        static const bool mfma_on = []() { const char* e = getenv("NNHIP_CONV_WGRAD_MFMA"); return !e || atoi(e) != 0; }();
-        const int Hp = (g.Ho - 1) * g.sh + 2 * g.dh + 1, Wp = (g.Wo - 1) * g.sw + 2 * g.dw + 1;
-        const int Lg = 4 * ((g.Ho * g.Wo + 3) / 4), nt = (ncols + 15) / 16;
-        const int nt_inst = nt <= 3 ? nt : nt <= 5 ? 5 : 10;   // the instantiation that will run (its LDS meeting area is 16*NT wide)
-        size_t m_lds = ((size_t)g.Cin * Hp * Wp + 4 + (size_t)g.Cout * Lg) * sizeof(float);
-        const size_t m_red = (size_t)4 * 16 * 16 * nt_inst * sizeof(float);
-        if (m_lds < m_red) m_lds = m_red;
-        int rc;
-        if (mfma_on && nt <= 10 && m_lds <= 60 * 1024) {
-            rc = nt <= 1 ? launch_mfma_wgrad<1>(X, dO, part, g, ncols, blocks, m_lds, st)
-               : nt <= 2 ? launch_mfma_wgrad<2>(X, dO, part, g, ncols, blocks, m_lds, st)
-               : nt <= 3 ? launch_mfma_wgrad<3>(X, dO, part, g, ncols, blocks, m_lds, st)
-               : nt <= 5 ? launch_mfma_wgrad<5>(X, dO, part, g, ncols, blocks, m_lds, st)
-                         : launch_mfma_wgrad<10>(X, dO, part, g, ncols, blocks, m_lds, st);
-            if (rc) return rc;
-            return conv_reduce(part, dW, db, blocks, g.Cout, Nw, ncols, st, deferred);
-        }
-        const int cip = g.Cin <= 1 ? 1 : g.Cin <= 2 ? 2 : g.Cin <= 4 ? 4 : g.Cin <= 8 ? 8 : 16;
-        const size_t red = (size_t)4 * (g.Cout <= 8 ? 8 : 16) * (cip * 9 + 1) * sizeof(float);
-        if (wg_lds < red) wg_lds = red;
-#define NNHIP_WG(CO_)                                                                                                        \
-        (cip == 1 ? launch_direct_wgrad<CO_, 1>(X, dO, part, g, ncols, blocks, wg_lds, st)                                      \
-         : cip == 2 ? launch_direct_wgrad<CO_, 2>(X, dO, part, g, ncols, blocks, wg_lds, st)                                    \
-         : cip == 4 ? launch_direct_wgrad<CO_, 4>(X, dO, part, g, ncols, blocks, wg_lds, st)                                    \
-         : cip == 8 ? launch_direct_wgrad<CO_, 8>(X, dO, part, g, ncols, blocks, wg_lds, st)                                    \
-                    : launch_direct_wgrad<CO_, 16>(X, dO, part, g, ncols, blocks, wg_lds, st))
-        rc = g.Cout <= 8 ? NNHIP_WG(8) : NNHIP_WG(16);
-#undef NNHIP_WG
-        if (rc) return rc;
-        return conv_reduce(part, dW, db, blocks, g.Cout, Nw, ncols, st, deferred);
-    } else if (dW || db) {
-        if (int rc = conv_mfma_wgrad(X, dO, dW, db, g, st)) return rc;
-    }
-    return 0;
+    if (!dW && !db) return 0;
+    // the small-channel kernels keep an image and its dO in LDS: the 16x16x4-MFMA kernel when its padded image + zero-padded dO fit
+    // too (mfma_wgrad_plan), else the direct kernel
+    const size_t wg_lds = ((size_t)g.Cin * g.H * g.W + (size_t)g.Cout * g.Ho * g.Wo) * sizeof(float);
+    if (direct && g.kh == 3 && g.kw == 3 && wg_lds <= 60 * 1024)
+        return conv_small_wgrad("nnhipConv2dBackward", X, dO, nullptr, mfma_wgrad_plan(g), wg_lds, dW, db, g, st);
+    return conv_mfma_wgrad(X, dO, dW, db, g, st);
 }

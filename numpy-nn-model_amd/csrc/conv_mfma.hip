@@ -286,7 +286,7 @@ static int launch_conv_tap(const float* W, const float* Src, const float* bias, 
         int d = 0, n = 0;
         return (hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
     }();
-    static const bool split_on = []() { const char* e = getenv("NNHIP_CONV_TAIL_SPLIT"); return !e || atoi(e) != 0; }();
+    static const bool split_on = env_int("NNHIP_CONV_TAIL_SPLIT", 1) != 0;
     const int64_t slots = (int64_t)cus * (wm == 2 ? 2 : 3);
     const int T = taps * (Csp / BK);
     int64_t tn_main = (((tiles_n * tiles_m) / slots) * slots) / tiles_m;   // pixel tiles of the whole rounds
@@ -755,7 +755,7 @@ int conv_mfma_wgrad(const float* X, const float* dO, float* dW, float* db, const
     a.tpi = (int)ceil_div(HWo, BK);
     // per-image k-tiles pad every image to a multiple of BK pixels (2x2 maps: 4 of 32 used); when that wastes more than ~3 % the
     // reduction index is flattened over (image, pixel) instead (FLAT: exact divisions by Ho*Wo and Wo per tile, no padding)
-    static const int flat_mode = []() { const char* e = getenv("NNHIP_CONV_WGRAD_FLAT"); return e ? atoi(e) : -1; }();   // dev knob: 0 never, 1 always
+    static const int flat_mode = env_int("NNHIP_CONV_WGRAD_FLAT", -1);   // dev knob: 0 never, 1 always
     const int64_t Ktot = (int64_t)g.B * HWo;
     const bool flat = flat_mode >= 0 ? flat_mode != 0 : (int64_t)a.tpi * BK * 32 > (int64_t)HWo * 33;
     a.ktiles = (int)ceil_div(Ktot, BK);
@@ -768,7 +768,7 @@ int conv_mfma_wgrad(const float* X, const float* dO, float* dW, float* db, const
     // the layer only, not on which outputs were asked for: db alone sums the same chunks in the same order as db next to dW
     int64_t chunks = 512 / (a.tiles_m * tgroups * cblks);
     if (chunks < 1) chunks = 1;
-    static const int min_kt = []() { const char* e = getenv("NNHIP_CONV_WGRAD_MINKT"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v; }();
+    static const int min_kt_env = env_int("NNHIP_CONV_WGRAD_MINKT", 4), min_kt = min_kt_env < 1 ? 1 : min_kt_env;
     if (chunks > ceil_div(ktiles, min_kt)) chunks = ceil_div(ktiles, min_kt);
     a.tpc = (int)ceil_div(ktiles, chunks);
     a.chunks = (int)ceil_div(ktiles, a.tpc);

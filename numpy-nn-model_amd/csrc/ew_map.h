@@ -36,7 +36,7 @@ __device__ __forceinline__ void ew_store(float4* p, float4 v, int nt) {
     else *p = v;
 }
 static int ew_nt(int64_t n) {
-    static const int forced = []() { const char* e = getenv("NNHIP_EW_NT"); return e ? atoi(e) : -1; }();
+    static const int forced = env_int("NNHIP_EW_NT", -1);
     if (forced >= 0) return forced;
     return n * 4 >= ((int64_t)128 << 20) ? 1 : 0;
 }

@@ -540,7 +540,7 @@ long long linear_gemv_launches();      // linear_gemv.hip
 static int gemm_f32_uneven_split(const float* A, const float* B, float* C, float* asum, int64_t M, int64_t N, int64_t K, int64_t lda,
                                  int64_t ldb, int64_t ldc, int64_t K1, hipStream_t st);
 static long long g_gemm_launches[4] = {0, 0, 0, 0};
-static int g_gemm_lockstep = []() { const char* e = getenv("NNHIP_GEMM_LOCKSTEP"); return e && atoi(e) == 1 ? 1 : 0; }();
+static int g_gemm_lockstep = env_int("NNHIP_GEMM_LOCKSTEP", 0) == 1 ? 1 : 0;
 static int g_gemm_mode = -1;    // -1: not initialised (NNHIP_GEMM_MODE decides), 0: exact fp32 MFMA, 1: split-bf16
 static int gemm_mode() {
     if (g_gemm_mode < 0) {
@@ -592,8 +592,8 @@ int gemm_f32_add(const float* A, const float* B, float* C, const float* bias, co
 int gemm_f32_linear_backward_small(const float* X, const float* W, const float* dO, float* dX, float* dW, float* db, int64_t rows,
                                    int64_t in, int64_t out, const float* addend, const float* dact_arg, int dact, float beta,
                                    hipStream_t st) {
-    static const int small_on = []() { const char* e = getenv("NNHIP_GEMM_SMALL"); return e ? atoi(e) : 1; }();
-    static const int pair_on = []() { const char* e = getenv("NNHIP_GEMM_PAIR"); return e ? atoi(e) : 1; }();
+    static const int small_on = env_int("NNHIP_GEMM_SMALL", 1);
+    static const int pair_on = env_int("NNHIP_GEMM_PAIR", 1);
     if (!small_on || !pair_on || gemm_mode() != 0 || !dX || !dW || rows <= 0 || in <= 0 || out <= 0) return 0;
     if (!gemm_small_wanted(rows, in, out, 1, out, in, true, false) || !gemm_small_wanted(out, in, rows, 1, out, in, false, false)) return 0;
     const int rc = gemm_small_linear_backward(X, W, dO, dX, dW, db, rows, in, out, addend, dact_arg, dact, beta, st);
@@ -634,14 +634,14 @@ int gemm_f32_ex(const float* A, const float* B, float* C, const float* bias, flo
         ++g_gemm_launches[1];
         return gemm_pst(A, B, C, bias, preact, M, N, K, lda, ldb, ldc, b_kmajor, alpha, act, beta, dswish, dact, st);
     }
-    static const int small_on = []() { const char* e = getenv("NNHIP_GEMM_SMALL"); return e ? atoi(e) : 1; }();
+    static const int small_on = env_int("NNHIP_GEMM_SMALL", 1);
     if (small_on && gemm_small_wanted(M, N, K, batch, lda, ldb, a_kmajor, b_kmajor)) {
         ++g_gemm_launches[2];
         return gemm_small(A, B, C, bias, preact, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, alpha, act, beta, asum, addend,
                           dswish, dact, st);
     }
     {   // one under-filled generation of a dW-type GEMM: uneven two-way split (gemm_f32_uneven_split)
-        static const int uneven_on = []() { const char* e = getenv("NNHIP_GEMM_UNEVEN"); return e ? atoi(e) : 1; }();
+        static const int uneven_on = env_int("NNHIP_GEMM_UNEVEN", 1);
         const int64_t t = ceil_div(M, BM) * ceil_div(N, BN);
         if (uneven_on && !a_kmajor && !b_kmajor && batch == 1 && !bias && !preact && !addend && !dswish &&
             act == ACT_NONE && alpha == 1.0f && t > 256 && t <= 496 && K >= 4096 && (K & 7) == 0 && (M & 3) == 0 && (N & 3) == 0 &&
@@ -649,7 +649,7 @@ int gemm_f32_ex(const float* A, const float* B, float* C, const float* bias, flo
             K * ldb + 128 < ((int64_t)1 << 30)) {
             // (the split that finishes both kinds together is ~3.4 % below K t / 512: a long block runs a little faster while the
             //  other slot of its CU is between short blocks -- swept on the head's 472 tiles: 456 of 512 k-tiles, not 472)
-            static const int bias_tiles = []() { const char* e = getenv("NNHIP_UNEVEN_BIAS"); return e ? atoi(e) : 0; }();   // dev knob
+            static const int bias_tiles = env_int("NNHIP_UNEVEN_BIAS", 0);   // dev knob
             const int64_t K1 = (K * t * 966 / ((int64_t)512 * 1000) + 31) / 32 * 32 + 32 * bias_tiles;
             if (K - K1 >= 256) {
                 ++g_gemm_launches[gemm_mode() == 1 ? 3 : 0];
@@ -682,12 +682,12 @@ int gemm_f32_ex(const float* A, const float* B, float* C, const float* bias, flo
     // (few = up to 64 tiles: 48 lone blocks of a 430 x 512 -> 1536 projection -- the notebook's batch-4 GPT -- walk 16 k-tiles at
     //  ~1.7 us each, 27 us for 0.7 GFLOP; split 8 ways + reduce they take ~12: that workload 242 -> 262 it/s.  16 / 48 / 64 / 96 / 128
     //  swept: 242 / 254 / 262 / 263 / 262.)
-    static const int few_tiles = []() { const char* e = getenv("NNHIP_SPLITK_FEW"); return e ? atoi(e) : 64; }();   // dev knob
+    static const int few_tiles = env_int("NNHIP_SPLITK_FEW", 64);   // dev knob
     const bool few = tiles <= few_tiles && K >= 256;
-    static const int tile_lim = []() { const char* e = getenv("NNHIP_SPLITK_TILES"); return e ? atoi(e) : 192; }();
+    static const int tile_lim = env_int("NNHIP_SPLITK_TILES", 192);
     if (batch == 1 && tiles < tile_lim && (K >= 1024 || few)) {
-        static const int slots = []() { const char* e = getenv("NNHIP_SPLITK_SLOTS"); return e ? atoi(e) : 512; }();   // dev knobs
-        static const int smax = []() { const char* e = getenv("NNHIP_SPLITK_MAX"); return e ? atoi(e) : 32; }();
+        static const int slots = env_int("NNHIP_SPLITK_SLOTS", 512);   // dev knobs
+        static const int smax = env_int("NNHIP_SPLITK_MAX", 32);
         int64_t s = slots / tiles;
         const int64_t max_by_k = few ? K / 64 : K / 256;
         if (s > max_by_k) s = max_by_k;
@@ -831,13 +831,13 @@ static int gemm_f32_uneven_split(const float* A, const float* B, float* C, float
 // blocks, an under-filled generation): 22.99 -- few fat chunks (a quarter of the slab traffic) win as long as a flush has >= ~700
 // blocks; four chunks keep a small flush (a DP segment boundary) from falling under that.
 static int64_t wgrad_chunk(int64_t K) {
-    static const int64_t forced = []() { const char* e = getenv("NNHIP_WGRAD_CHUNK"); return (int64_t)(e ? atoi(e) : 0); }();   // dev knob
+    static const int64_t forced = env_int("NNHIP_WGRAD_CHUNK", 0);   // dev knob
     if (forced > 0) return ceil_div(forced, (int64_t)32) * 32;
     const int64_t c = ceil_div(ceil_div(K, (int64_t)4), (int64_t)32) * 32;
     return c < 1024 ? 1024 : c;
 }
 bool gemm_f32_wgrad_group_ok(const WgradJob& j) {
-    static const int on = []() { const char* e = getenv("NNHIP_WGRAD_GROUP_KERNEL"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NNHIP_WGRAD_GROUP_KERNEL", 1);
     if (!on) return false;                                   // (both GEMM modes: the group kernel exists for each)
     if (j.M <= 0 || j.N <= 0 || j.K < 4096 || (j.K & 7)) return false;
     if ((j.M & 3) || (j.N & 3) || !aligned16(j.A) || !aligned16(j.B) || !aligned16(j.C)) return false;

@@ -398,7 +398,7 @@ static int pst_epi(bool b_kmajor, int act, const float* preact, const float* dsw
 // NNHIP_GEMM_PST: 0 = never, 1 (default) = when the conditions hold, 2 = also for long reductions
 bool gemm_pst_wanted(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const float* A, const float* B,
                      const float* C, const float* bias, bool b_kmajor, int act, const float* preact, const float* dswish, int dact) {
-    static const int on = []() { const char* e = getenv("NNHIP_GEMM_PST"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NNHIP_GEMM_PST", 1);
     if (!on) return false;
     const int epi = pst_epi(b_kmajor, act, preact, dswish, dact);
     if (epi < 0) return false;
@@ -429,7 +429,7 @@ int gemm_pst(const float* A, const float* B, float* C, const float* bias, float*
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.alpha = alpha; p.beta = beta;
     p.tiles_m = (int)(M / 128); p.tiles_n = (int)ceil_div(N, 128); p.total = p.tiles_m * p.tiles_n;
-    static const int stagger = []() { const char* e = getenv("NNHIP_PST_STAGGER"); return e ? atoi(e) : 1; }();
+    static const int stagger = env_int("NNHIP_PST_STAGGER", 1);
     p.stagger = stagger;
     const size_t lds = 2 * PSTAGE * sizeof(float);
     const dim3 grid((unsigned)pst_slots()), block(NT);

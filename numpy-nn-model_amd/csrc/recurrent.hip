@@ -306,7 +306,7 @@ __global__ __launch_bounds__(kRecThreads, 1) void lstm_bwd_kernel(const LstmBwdA
 }
 
 static bool lstm_resident_on() {
-    static const int on = []() { const char* e = getenv("NNHIP_LSTM_RESIDENT"); return e ? atoi(e) : 1; }();   // A/B knob
+    static const int on = env_int("NNHIP_LSTM_RESIDENT", 1);   // A/B knob
     return on != 0;
 }
 

@@ -451,7 +451,7 @@ void colsum_cleanup() { g_csq.cleanup(); }
 // flush: the arena, else nullptr (the caller uses the shared workspace and finishes at once).  The arena has room for a whole queue
 // of the same size.
 static float* colsum_partials(size_t floats, int njobs, int sw, bool vec, hipStream_t st, int* rc) {
-    static const bool on = []() { const char* e = getenv("NNHIP_COLSUM_DEFER"); return !e || atoi(e) != 0; }();
+    static const bool on = env_int("NNHIP_COLSUM_DEFER", 1) != 0;
     *rc = 0;
     if (!on || !wgrad_defer_on()) return nullptr;
     return g_csq.reserve(floats, njobs, sw << 1 | (vec ? 1 : 0), st, floats * CSQ_MAX, rc);
@@ -1748,7 +1748,7 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_bwd_looped(float* __restri
 // (>= 128 MB: the producer's output is long gone from the 32 MB of L2 and mostly from the 256 MB MALL) and its rows are
 // whole 128-B lines (see RowTile::load).  NNHIP_ROW_NT=0/1 forces it off/on (developer switch).
 static int row_streaming(int64_t rows, int64_t cols, int64_t ld) {
-    static const int forced = []() { const char* e = getenv("NNHIP_ROW_NT"); return e ? atoi(e) : -1; }();
+    static const int forced = env_int("NNHIP_ROW_NT", -1);
     if (forced >= 0) return forced;
     return (rows * cols * 4 >= ((int64_t)128 << 20) && ((ld * 4) & 127) == 0) ? 1 : 0;
 }

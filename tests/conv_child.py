@@ -6,7 +6,9 @@ all three outputs, then dX only, dW only, db only -- every output in a NaN-fille
 
 python tests/conv_child.py [DUMP.npz]   runs child_cases() under whatever the environment says and prints ONE JSON object: the switches it
 saw and, per case, the worst error / bound ratio and a sha256 digest of every output, and whatever invariant (fences, NaN left,
-separately requested outputs not bit-identical to the joint call) it found broken.  DUMP.npz: every case's dX is saved there too."""
+separately requested outputs not bit-identical to the joint call) it found broken.  DUMP.npz: every case's dX is saved there too.
+
+python tests/conv_child.py --fused-off   fused_off_main(): the three switches that are no part of the dispatch table."""
 import ctypes
 import hashlib
 import json
@@ -181,5 +183,40 @@ def main():
     return 0
 
 
+FUSED_OFF = ("NNHIP_CONV_POOL_FWD", "NNHIP_CONV_POOLED_WGRAD", "NNHIP_CONV_DEFER_REDUCE")
+
+
+def fused_off_main():
+    """python tests/conv_child.py --fused-off, started with the three switches of FUSED_OFF at 0 (they are no part of conv_ref.ENV: route()
+    has no entry they move).  Prints ONE JSON object: the switches it saw, what the two ...Ok queries answer for the first fused cases, and
+    the digests of nt_c8_o16's dW and db from nnhipConv2dBackward under nnhipWeightGradDefer(1), read after the flush."""
+    import torch
+    import neunet_hip
+    from conv_ref import BY_NAME, POOL_FWD_CASES, POOL_WGRAD_CASES
+    from vision_ref import PoolDesc
+    neunet_hip.load_library()
+
+    def pool_of(d, kh=2, kw=2):
+        return PoolDesc(d.B, d.Cout, *d.out_hw(), kh, kw)
+    _, df, _ = POOL_FWD_CASES[0]
+    _, dw, win, _ = POOL_WGRAD_CASES[0]
+    res = dict(env={v: os.environ.get(v, "") for v in FUSED_OFF},
+               pool_fwd_ok=call("nnhipConv2dLeakyMaxPoolForwardOk", cdesc(df), cpool(pool_of(df))),
+               pooled_wgrad_ok=call("nnhipConv2dWeightGradPooledOk", cdesc(dw), cpool(pool_of(dw, *win))))
+    d = BY_NAME["nt_c8_o16"].desc
+    X, Wt, _, dO = make_inputs("nt_c8_o16", d)
+    call("nnhipWeightGradDefer", 1)
+    try:
+        out, _ = backward(d, dev(X), dev(Wt), dev(dO))
+        call("nnhipWeightGradFlush")
+    finally:
+        call("nnhipWeightGradDefer", 0)
+    torch.cuda.synchronize()
+    res["guards_intact"] = all(f.guards_intact() for f in out.values())
+    res["digests"] = {k: digest(out[k].view) for k in ("dW", "db")}
+    print(json.dumps(res))
+    return 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(fused_off_main() if sys.argv[1:] == ["--fused-off"] else main())

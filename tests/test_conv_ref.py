@@ -77,8 +77,8 @@ def test_fused_chain_agrees_with_oracle(name, d, why, alpha):
 
 # ===================================================================================================== coverage
 # Every kernel instantiation the host code of conv2d.hip / conv_mfma.hip can launch on behalf of Conv2d, from the hipLaunchKernelGGL and
-# launch_* sites (nnhipConv2dForward, conv_pool_forward, nnhipConv2dBackward, nnhipConv2dWeightGradPooled, launch_conv_tap,
-# conv_mfma_wgrad, conv_reduce, conv_reduce_group_launch).
+# launch_* sites (conv_direct_forward, conv_pool_forward, conv_direct_dgrad, conv_small_wgrad's launch_mfma_wgrad_plan and
+# launch_direct_wgrad_width, launch_conv_tap, conv_mfma_wgrad, conv_reduce_launch, conv_reduce_group_launch).
 WANTED = [
     "conv_direct_fwd_kernel<4>", "conv_direct_fwd_kernel<8>", "conv_direct_fwd_kernel<16>", "conv_direct_fwd_quad_kernel<8>",
     "conv_direct_fwd_quad_kernel<16>", "conv_direct_dgrad_kernel<4>", "conv_direct_dgrad_kernel<8>", "conv_direct_dgrad_kernel<16>",

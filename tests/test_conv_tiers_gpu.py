@@ -509,6 +509,39 @@ def test_switch_setting(hip, setting):
     assert moved >= MIN_MOVED[setting]
 
 
+def test_fused_switches_off(hip):
+    """NNHIP_CONV_POOL_FWD=0, NNHIP_CONV_POOLED_WGRAD=0 and NNHIP_CONV_DEFER_REDUCE=0 together, in a fresh process (conv_child.py
+    --fused-off: a few seconds, three small shapes).  route() has no entry they move, so they are no part of conv_ref.ENV; their default
+    state is what pf_*, pw_* and test_deferred_reduce_queue run.  Off: the two queries answer 0 for the first fused cases (this process,
+    with the defaults, answers 1), and nt_c8_o16's dW and db from a deferred nnhipConv2dBackward -- reduced at once, not queued -- are
+    the bits of the default run."""
+    from conv_child import FUSED_OFF
+    if _dead:
+        pytest.fail(f"an earlier child process ended abnormally ({_dead[0]}); no further child is started")
+    _, df, _ = POOL_FWD_CASES[0]
+    _, dw, win, _ = POOL_WGRAD_CASES[0]
+    assert call("nnhipConv2dLeakyMaxPoolForwardOk", cdesc(df), cpool(pool_of(df))) == 1
+    assert call("nnhipConv2dWeightGradPooledOk", cdesc(dw), cpool(pool_of(dw, *win))) == 1
+    base = default_run("nt_c8_o16")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("NNHIP_CONV_")}
+    env.update({k: "0" for k in FUSED_OFF})
+    try:
+        r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_child.py"), "--fused-off"], env=env,
+                           capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+    except subprocess.TimeoutExpired:
+        _dead.append("fused-off: timeout")
+        pytest.fail(_dead[0])
+    if r.returncode < 0 or r.returncode in (134, 139):
+        _dead.append(f"fused-off: status {r.returncode}")
+        pytest.fail(_dead[0] + "\n" + r.stderr[-4000:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert res["env"] == {k: "0" for k in FUSED_OFF}
+    assert res["pool_fwd_ok"] == 0 and res["pooled_wgrad_ok"] == 0
+    assert res["guards_intact"]
+    assert res["digests"] == {k: base["digests"][k] for k in ("dW", "db")}, "deferral ignored: dW / db differ from the default run"
+
+
 def test_quad2_against_quad(hip):
     """conv2d.hip on conv_direct_dgrad_quad2_kernel: "Same products in the same order per output (co = s, s + 4, ...; taps in order;
     quad tree)" as the position-per-quad kernel.  That is a statement about the source, not about the bits: the compiler contracts
