@@ -595,6 +595,31 @@ int nnhipMaxPool2dLeakyForward(float* out, int32_t* argmax, const float* X, floa
                                nnhipStream_t stream);
 int nnhipMaxPool2dLeakyBackward(float* dX, const float* dY, const int32_t* argmax, const float* pooled, float alpha,
                                 const nnhipPool2dDesc* d, nnhipStream_t stream);
+/* AvgPool2d (neunet/nn/layers/avgpool2d.py:14-46, :126-172), NCHW float32, on the same descriptor; dh / dw must be 0 or 1 (the
+ * layer has no dilation).  pad = (up, down, left, right), padded with zeros that COUNT in the mean:
+ *   out[b,c,ho,wo] = (sum of the window's taps inside the image) / (kh kw),   Ho = (H + pu + pd - kh) / sh + 1 (floor), Wo likewise.
+ * A window wholly inside the padding gives 0.  Backward is a gather: dX[b,c,y,x] = (sum of dY over the windows that cover (y, x), in
+ * (ho, wo) order) / (kh kw); an input pixel no window covers (stride > kernel, rows / columns left over by the floor) gets +0.  Both
+ * entries write every element of their output exactly once, in ONE launch, with no memset, atomics or workspace: reruns are
+ * bit-identical and the launches may be captured into a hipGraph.  NaN and +-inf propagate as the arithmetic gives.
+ * Three kernel tiers, by descriptor alone (nnhipAvgPool2dTier): TILES when kernel == stride, no padding and
+ * H = Ho kh, W = Wo kw (one thread per window; 16-byte accesses only where W and the base pointers allow); GLOBAL_WAVE / _BLOCK
+ * when kh = H, kw = W, no padding (one wave per plane up to 1024 elements, one block per plane above); GENERAL otherwise.
+ * Refused before any launch, outputs untouched -- NNHIP_EINVAL: a NULL pointer or descriptor; B, C, H, W, kh, kw, sh or sw < 1 (so
+ * B * C == 0 is not accepted); a negative pad; dilation > 1; an output extent < 1; an input or output of 2^31 elements or more (the
+ * kernels index with 32 bits).  NNHIP_EALIGN: a pointer that is not 4-byte aligned.  ABI 225 */
+int nnhipAvgPool2dForward(float* out, const float* X, const nnhipPool2dDesc* d, nnhipStream_t stream);
+int nnhipAvgPool2dBackward(float* dX, const float* dY, const nnhipPool2dDesc* d, nnhipStream_t stream);
+#define NNHIP_AVGPOOL_TIER_GENERAL 0
+#define NNHIP_AVGPOOL_TIER_TILES 1
+#define NNHIP_AVGPOOL_TIER_GLOBAL_WAVE 2
+#define NNHIP_AVGPOOL_TIER_GLOBAL_BLOCK 3
+/* The tier both entries take for this descriptor under the current route (host only, no device call), or NNHIP_EINVAL. */
+int nnhipAvgPool2dTier(const nnhipPool2dDesc* d);
+#define NNHIP_AVGPOOL_ROUTE_AUTO 0
+#define NNHIP_AVGPOOL_ROUTE_GENERAL 1    /* every descriptor on the general tier: for tests and A/B timing (tools/kbench.py) */
+/* Process-wide; returns the previous route.  An unknown value changes nothing. */
+int nnhipSetAvgPool2dRoute(int route);
 /* Conv2d weight / bias gradient straight from the gradient of a MaxPool2d that consumed the conv's output, through an optional
  * LeakyReLU (the backward of conv2d.py:16-115 composed with maxpool2d.py:11-82 and activations.py:72-84, restricted to dW, db):
  *   dW, db of   P = MaxPool2d([LeakyReLU(] Conv2d(X) [; alpha)])   given dP, the pool's window-local arg-max and -- with the

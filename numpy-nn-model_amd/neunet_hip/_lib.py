@@ -210,6 +210,10 @@ _SIGNATURES = {
     "nnhipMaxPool2dBackward": (ctypes.c_int, [P, P, P, POINTER(Pool2dDesc), c_void_p]),
     "nnhipMaxPool2dLeakyForward": (ctypes.c_int, [P, P, P, c_float, POINTER(Pool2dDesc), c_void_p]),
     "nnhipMaxPool2dLeakyBackward": (ctypes.c_int, [P, P, P, P, c_float, POINTER(Pool2dDesc), c_void_p]),
+    "nnhipAvgPool2dForward": (ctypes.c_int, [P, P, POINTER(Pool2dDesc), c_void_p]),
+    "nnhipAvgPool2dBackward": (ctypes.c_int, [P, P, POINTER(Pool2dDesc), c_void_p]),
+    "nnhipAvgPool2dTier": (ctypes.c_int, [POINTER(Pool2dDesc)]),
+    "nnhipSetAvgPool2dRoute": (ctypes.c_int, [ctypes.c_int]),
     "nnhipConv2dWeightGradPooledOk": (ctypes.c_int, [POINTER(Conv2dDesc), POINTER(Pool2dDesc)]),
     "nnhipConv2dWeightGradPooled": (ctypes.c_int, [P, P, P, P, c_float, P, P, POINTER(Conv2dDesc), POINTER(Pool2dDesc), c_void_p]),
     "nnhipConv2dLeakyMaxPoolForwardOk": (ctypes.c_int, [POINTER(Conv2dDesc), POINTER(Pool2dDesc)]),
@@ -282,7 +286,7 @@ _SIGNATURES = {
 }
 _NO_STATUS = {"nnhipVersion", "nnhipLinearReLULinearBackwardFits", "nnhipBatchNorm2dLinearSigmoidMSEFits", "nnhipConv2dLeakyMaxPoolStatsBlocks", "nnhipGetLastErrorString", "nnhipCreateFusedOptimizer", "nnhipGetGemmMode", "nnhipGetGemmLockstep", "nnhipConv2dWeightGradPooledOk", "nnhipConv2dLeakyMaxPoolForwardOk", "nnhipGemmLaunchCount",
               "nnhipWeightGradPending", "nnhipGetLinearGemv", "nnhipSetConvTransposeRoute", "nnhipGetConvTransposeRoute",
-              "nnhipConvTranspose2dPlan", "nnhipTensorOpsLastTier"}
+              "nnhipConvTranspose2dPlan", "nnhipTensorOpsLastTier", "nnhipAvgPool2dTier", "nnhipSetAvgPool2dRoute"}
 
 _dll = None
 _funcs: dict = {}

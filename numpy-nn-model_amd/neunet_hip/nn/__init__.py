@@ -15,7 +15,8 @@ from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear a
                            HIPBCELoss as BCELoss, HIPGRU as GRU, HIPRNN as RNN, HIPBidirectional as Bidirectional,
                            HIPSoftplus as Softplus, HIPSoftsign as Softsign, HIPMish as Mish, HIPTanhExp as TanhExp,
                            HIPELU as ELU, HIPSELU as SELU, HIPLogSoftmax as LogSoftmax, HIPNLLLoss as NLLLoss,
-                           HIPL1Loss as L1Loss, HIPKLDivLoss as KLDivLoss)
+                           HIPL1Loss as L1Loss, HIPKLDivLoss as KLDivLoss, HIPAvgPool2d as AvgPool2d,
+                           HIPZeroPad2d as ZeroPad2d, HIPFlatten as Flatten)
 
 
 class CrossEntropyLoss(HIPCrossEntropyLoss):

@@ -16,3 +16,4 @@ from .recurrent import HIPLSTM, HIPGRU, HIPRNN, HIPBidirectional  # noqa: F401
 from .layernorm import HIPLayerNorm  # noqa: F401
 from .causal_attention import HIPCausalSelfAttention, KVCache  # noqa: F401
 from .batchnorm1d import HIPBatchNorm1d  # noqa: F401
+from .pooling import HIPAvgPool2d, HIPFlatten, HIPZeroPad2d  # noqa: F401

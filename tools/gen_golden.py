@@ -1902,10 +1902,112 @@ def gen_tape_index():
     save("tape_index", **arrs)
 
 
+def gen_shape_layers():
+    """shape_layers.npz: AvgPool2d (forward and input gradient, on the rows of tests/avgpool_ref.py's case table whose vertical and
+    horizontal padding are equal -- the reference's backward sizes its buffer from padding[0], padding[1] of the 4-tuple and cannot
+    run on the others), ZeroPad2d (forward only: the reference's backward is never reached, it assigns `_backward` instead of
+    `grad_fn`) and Flatten (a reshape: output and input gradient).  nn_layer_names.txt: the names neunet/nn/layers/__init__.py
+    exports, one per line -- a list of names, nothing else."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import avgpool_ref as AR
+    seed_layers(225)
+    rng = np.random.default_rng(5)
+    arrs = {}
+    for case in AR.CASES:
+        if not AR.equal_padding(case):
+            continue
+        shape, k, s, p, _ = case
+        tag = "avg/" + AR.case_id(case)
+        X = rng.standard_normal(shape).astype(F32)
+        x = T(X)
+        y = nn.AvgPool2d(k, s, p)(x)
+        dY = rng.standard_normal(y.shape).astype(F32)
+        y.backward(dY)
+        arrs.update({f"{tag}/X": X, f"{tag}/Y": np.asarray(y.data, F32), f"{tag}/dY": dY, f"{tag}/dX": np.asarray(x.grad, F32)})
+    for tag, shape, p in [("int", (2, 3, 4, 4), 1), ("pair", (1, 2, 3, 5), (2, 1)), ("four", (1, 2, 3, 5), (1, 2, 3, 0)), ("three_d", (3, 4, 4), (1, 2))]:
+        X = rng.standard_normal(shape).astype(F32)
+        arrs.update({f"pad/{tag}/X": X, f"pad/{tag}/Y": np.asarray(nn.ZeroPad2d(p)(T(X)).data, F32),
+                     f"pad/{tag}/padding": np.array(AR.pair(p), np.int64)})
+    for tag, dims in [("default", ()), ("d0_1", (0, 1)), ("dm2", (-2,)), ("d0_m1", (0, -1))]:
+        X = rng.standard_normal((2, 3, 4, 5)).astype(F32)
+        x = T(X)
+        y = nn.Flatten(*dims)(x)
+        dY = rng.standard_normal(y.shape).astype(F32)
+        y.backward(dY)
+        arrs.update({f"flat/{tag}/X": X, f"flat/{tag}/Y": np.asarray(y.data, F32), f"flat/{tag}/dY": dY, f"flat/{tag}/dX": np.asarray(x.grad, F32),
+                     f"flat/{tag}/dims": np.array(dims, np.int64)})
+    save("shape_layers", **arrs)
+    import neunet.nn.layers as layers
+    names = sorted(n for n in vars(layers) if isinstance(getattr(layers, n), type))
+    with open(os.path.join(OUT, "nn_layer_names.txt"), "w") as fh:
+        fh.write("\n".join(names) + "\n")
+
+
+LENET5_SEED = 0
+
+
+def gen_lenet5():
+    """lenet5_*.npz: one training step of LeNet-5 (examples/lenet5.py's class on the reference's layers) at batch 8: ZeroPad2d(2),
+    two 5x5 convolutions each followed by Tanh and AvgPool2d(2), Flatten, Linear 400 -> 120 -> 84 -> 10 with Tanh between,
+    CrossEntropyLoss, Adam(lr 1e-3).  The padded input enters the model as a fresh leaf tensor: the reference cannot back-propagate
+    through its ZeroPad2d.  `unclear_share`: the share of parameter elements whose gradient is within rounding noise of zero, as
+    tests/test_convtranspose_gpu.py::test_ddpm_unet_step_vs_reference defines it (|g| <= 2e, e = 1e-4 max(|g|, rms(g), gscale))."""
+    seed_layers(226 + LENET5_SEED)
+    rng = np.random.default_rng(226 + LENET5_SEED)
+
+    class LeNet5(nn.Module):
+        def __init__(self):
+            self.pad = nn.ZeroPad2d(2)
+            self.conv1 = nn.Conv2d(1, 6, 5)
+            self.pool1 = nn.AvgPool2d(2)
+            self.conv2 = nn.Conv2d(6, 16, 5)
+            self.pool2 = nn.AvgPool2d(2)
+            self.flatten = nn.Flatten()
+            self.fc1 = nn.Linear(400, 120)
+            self.fc2 = nn.Linear(120, 84)
+            self.fc3 = nn.Linear(84, 10)
+            self.tanh = nn.Tanh()
+
+        def features(self, xp):
+            x = self.pool1(self.tanh(self.conv1(xp)))
+            x = self.pool2(self.tanh(self.conv2(x)))
+            x = self.flatten(x)
+            x = self.tanh(self.fc1(x))
+            x = self.tanh(self.fc2(x))
+            return self.fc3(x)
+
+    model = LeNet5()
+    params = model.parameters()
+    X = rng.uniform(-1, 1, (8, 1, 28, 28)).astype(F32)
+    Y = rng.integers(0, 10, 8).astype(np.int32)
+    arrs = {"X": X, "Y": Y, "n_params": np.int64(len(params)), "lr": np.float64(1e-3)}
+    for i, p in enumerate(params):
+        arrs[f"p{i}"] = p.data.copy()
+    opt = Adam(params, lr=1e-3)
+    opt.zero_grad()
+    xp = T(np.asarray(model.pad(T(X, requires_grad=False)).data, F32), requires_grad=False)
+    logits = model.features(xp)
+    loss = nn.CrossEntropyLoss()(logits, T(Y, dtype=np.int32, requires_grad=False))
+    loss.backward()
+    grads = [np.asarray(p.grad, F32).copy() for p in params]
+    opt.step()
+    arrs.update(Xpad=np.asarray(xp.data, F32), logits=np.asarray(logits.data, F32), loss=np.float64(loss.data))
+    for i, (g, p) in enumerate(zip(grads, params)):
+        arrs[f"g{i}"], arrs[f"p_after{i}"] = g, np.asarray(p.data, F32).copy()
+    gscale = float(np.median([np.sqrt(np.mean(g.astype(np.float64) ** 2)) for g in grads]))       # test_hip_parity.grad_list_scale
+    unclear = total = 0
+    for g in grads:
+        g64 = g.astype(np.float64)
+        e = 1e-4 * np.maximum(np.maximum(np.abs(g64), np.sqrt(np.mean(g64 ** 2))), gscale)
+        unclear, total = unclear + int((np.abs(g64) <= 2 * e).sum()), total + g64.size
+    arrs["unclear_share"] = np.float64(unclear / total)
+    save_parts("lenet5", arrs)
+
+
 GENERATORS = [gen_linear, gen_activations, gen_ce, gen_ce_weighted, gen_rmsnorm, gen_conv, gen_adam, gen_linear_swish, gen_mlp,
               gen_gpt, gen_vision, gen_maxpool_dilated, gen_lstm, gen_layernorm_gelu, gen_gpt2, gen_convtranspose, gen_ddpm, gen_seq2seq,
               gen_batchnorm1d, gen_gan, gen_vae, gen_vq, gen_gru, gen_rnn, gen_bidirectional, gen_optim_rules, gen_activations_losses,
-              gen_word2vec, gen_tape_ops, gen_conway, gen_tape_index]
+              gen_word2vec, gen_tape_ops, gen_conway, gen_tape_index, gen_shape_layers, gen_lenet5]
 
 
 def generate_all(out_dir=None, quiet=False):

@@ -430,6 +430,85 @@ def main():
                     print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
                           f"round medians {' '.join(f'{v:.4f}' for v in m)}")
 
+    def alternate(routes, rounds, label, nbytes):
+        """routes: {name: (forward fn, backward fn)}, alternating in this process for `rounds` rounds; per route and direction the
+        median of the round medians, the fastest launch and p10 - p90 of all timed launches; GB/s on the algorithmic bytes."""
+        samples = {(name, k): [] for name in routes for k in (0, 1)}
+        meds = {key: [] for key in samples}
+        for _ in range(rounds):
+            for name, fns in routes.items():
+                for k, fn in enumerate(fns):
+                    ms = bench_samples(fn, args.iters)
+                    samples[(name, k)].extend(ms)
+                    meds[(name, k)].append(float(np.median(ms)))
+        for k, direction in enumerate(("fwd", "bwd")):
+            for name in routes:
+                allms, m = np.array(samples[(name, k)]), np.array(meds[(name, k)])
+                report(f"{name} {direction} {label}", float(np.median(m)), float(allms.min()), nbytes=nbytes)
+                print(f"{'':34s} p10 {np.percentile(allms, 10):.4f}  p90 {np.percentile(allms, 90):.4f} ms over {allms.size} launches; "
+                      f"round medians {' '.join(f'{v:.4f}' for v in m)}")
+
+    if "avgpool" in only:
+        # AvgPool2d (nnhipAvgPool2d*, csrc/avgpool.hip): LeNet-5's two pools at batch 256, a large 2x2/2 pool and a global pool.  The
+        # tier the descriptor selects, the general tier forced on the same descriptor (nnhipSetAvgPool2dRoute), torch's avg_pool2d
+        # (its backward through torch.ops.aten.avg_pool2d_backward) and the read + write roof for the same bytes (the library's ReLU
+        # over (n_in + n_out) / 2 elements: tools/stream_roof.py's kernel at this footprint) ALTERNATE in this process.
+        from neunet_hip._lib import Pool2dDesc
+        F = torch.nn.functional
+        tiers = {0: "general", 1: "tiles", 2: "global_wave", 3: "global_block"}
+        for (B, C, H, W, k) in [(256, 6, 28, 28, 2), (256, 16, 10, 10, 2), (64, 64, 112, 112, 2), (256, 512, 7, 7, 7), (64, 64, 56, 56, 56)]:
+            d = Pool2dDesc(B, C, H, W, k, k, k, k, 0, 0, 0, 0, 1, 1)
+            X, dY = randn(B, C, H, W), randn(B, C, H // k, W // k)
+            Y, dX = torch.empty_like(dY), torch.empty_like(X)
+            n = (X.numel() + Y.numel()) // 2
+            sa, sb = torch.empty(n, device=dev), randn(n)
+            tier = tiers[call("nnhipAvgPool2dTier", ctypes.byref(d))]
+
+            def forced(entry, dst, src):
+                def run():
+                    prev = call("nnhipSetAvgPool2dRoute", 1)
+                    call(entry, dst, src, ctypes.byref(d), st)
+                    call("nnhipSetAvgPool2dRoute", prev)
+                return run
+
+            routes = {tier: (lambda: call("nnhipAvgPool2dForward", Y, X, ctypes.byref(d), st),
+                             lambda: call("nnhipAvgPool2dBackward", dX, dY, ctypes.byref(d), st)),
+                      "general": (forced("nnhipAvgPool2dForward", Y, X), forced("nnhipAvgPool2dBackward", dX, dY)),
+                      "torch": (lambda: F.avg_pool2d(X, k), lambda: torch.ops.aten.avg_pool2d_backward(dY, X, [k, k], [k, k], [0, 0], False, True, None)),
+                      "stream": (lambda: call("nnhipReLUForward", sa, sb, n, st), lambda: call("nnhipReLUForward", sa, sb, n, st))}
+            outs = {}
+            for name in (tier, "general"):
+                routes[name][0]()
+                routes[name][1]()
+                outs[name] = (Y.clone(), dX.clone())
+            ref = (F.avg_pool2d(X.double(), k), torch.ops.aten.avg_pool2d_backward(dY.double(), X.double(), [k, k], [k, k], [0, 0], False, True, None))
+            print(f"avgpool {B}x{C}x{H}x{W} k{k} [{tier}]: |{tier} - general| max Y {float((outs[tier][0] - outs['general'][0]).abs().max()):.2e} "
+                  f"dX {float((outs[tier][1] - outs['general'][1]).abs().max()):.2e}; vs float64 Y {float((outs[tier][0].double() - ref[0]).abs().max()):.2e} "
+                  f"dX {float((outs[tier][1].double() - ref[1]).abs().max()):.2e}")
+            alternate(routes, 5, f"{B}x{C}x{H}x{W} k{k}", 4.0 * (X.numel() + Y.numel()))
+
+    if "zeropad" in only:
+        # ZeroPad2d: nnhipSliceBackward as the pad, nnhipSliceForward as the crop (what nn.ZeroPad2d launches), beside
+        # torch.nn.functional.pad / a contiguous copy of the cropped view and the read + write roof for the same bytes.
+        from neunet_hip.tensor_ops import _i64, contiguous_strides
+        for (B, C, H, W, p) in [(256, 1, 28, 28, 2), (64, 64, 56, 56, 1)]:
+            X, G = randn(B, C, H, W), randn(B, C, H + 2 * p, W + 2 * p)
+            Y, dX = torch.empty_like(G), torch.empty_like(X)
+            n = (X.numel() + Y.numel()) // 2
+            sa, sb = torch.empty(n, device=dev), randn(n)
+            shp, pshp = _i64(X.shape), _i64(Y.shape)
+            start, step, strides = _i64((0, 0, p, p)), _i64((1, 1, 1, 1)), _i64(contiguous_strides(tuple(Y.shape)))
+            off = p * (W + 2 * p) + p
+            routes = {"slice": (lambda: call("nnhipSliceBackward", Y, X, 4, pshp, start, step, shp, st),
+                                lambda: call("nnhipSliceForward", dX, G, off, 0, 4, shp, strides, st)),
+                      "torch": (lambda: torch.nn.functional.pad(X, (p, p, p, p)), lambda: G[:, :, p:p + H, p:p + W].contiguous()),
+                      "stream": (lambda: call("nnhipReLUForward", sa, sb, n, st), lambda: call("nnhipReLUForward", sa, sb, n, st))}
+            routes["slice"][0]()
+            routes["slice"][1]()
+            print(f"zeropad {B}x{C}x{H}x{W} p{p}: pad == torch {bool(torch.equal(Y, torch.nn.functional.pad(X, (p, p, p, p))))}, "
+                  f"crop == torch {bool(torch.equal(dX, G[:, :, p:p + H, p:p + W]))}")
+            alternate(routes, 5, f"{B}x{C}x{H}x{W} p{p}", 4.0 * (X.numel() + Y.numel()))
+
     if "vq" in only:
         # The nearest-code search (nnhipVQNearest, csrc/vector_quantize.hip) against the composition a user would otherwise write on
         # torch: z @ E.T, the two norms, argmin, index_select -- an N x K matrix written and read back.  The two routes and a read-only
@@ -502,8 +581,6 @@ def main():
         # beside the same-shape kernel on the same output bytes and beside the torch expression; row / column / NCHW-channel reductions
         # beside torch.sum (algorithmic bytes: the input once); the fused broadcast backward (dB of a * b without the full-shape
         # gradient) beside the unfused pair (nnhipMul into a full-shape buffer, then the reduction).
-        import ctypes
-
         def i64(*v):
             return (ctypes.c_int64 * len(v))(*v)
 
@@ -560,8 +637,6 @@ def main():
         # a preallocated output where torch has an out= form, the bare expression otherwise: never an extra copy) and beside a plain
         # stream of the same footprint (`stream`: the float4 stream tools/stream_roof.py measures, nnhipReLUForward, over as many bytes
         # as the entry moves, half read and half written).
-        import ctypes
-
         def i64(*v):
             return (ctypes.c_int64 * max(len(v), 1))(*v)
 
