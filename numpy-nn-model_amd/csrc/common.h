@@ -199,6 +199,13 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 __device__ __forceinline__ float ld_dev_f32(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int ld_dev_i32(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// Class label i of an int16 / int32 / int64 array (lbytes = 2 / 4 / 8): the CrossEntropy and NLL kernels.
+__device__ __forceinline__ int64_t load_label(const void* labels, int64_t i, int lbytes) {
+    if (lbytes == 4) return reinterpret_cast<const int32_t*>(labels)[i];
+    if (lbytes == 8) return reinterpret_cast<const int64_t*>(labels)[i];
+    return reinterpret_cast<const int16_t*>(labels)[i];
+}
+
 // Counter-based random bits: a lowbias32-style integer hash of (seed, row, key).  The fused attention's dropout evaluates it per
 // (query row, key); nnhipSampleTopK (sample.hip) draws a row's uniform from key 0.  One definition: both must see the same bits.
 __device__ __forceinline__ unsigned at_rowkey(unsigned seed, unsigned row) { return (seed * 0x85EBCA6Bu + 0x9E3779B9u) ^ (row * 0xC2B2AE35u); }

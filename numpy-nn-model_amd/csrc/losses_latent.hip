@@ -118,15 +118,9 @@ struct NllArgs {
     int64_t ignore, C, inner, P;
     int lbytes;
 };
-// (the label loader of rowops.hip's CrossEntropy kernels, which is local to that file)
-__device__ __forceinline__ int64_t nll_label(const void* labels, int64_t i, int lbytes) {
-    if (lbytes == 4) return reinterpret_cast<const int32_t*>(labels)[i];
-    if (lbytes == 8) return reinterpret_cast<const int64_t*>(labels)[i];
-    return reinterpret_cast<const int16_t*>(labels)[i];
-}
 // true when position p counts: its weight and the offset of its logp entry
 __device__ __forceinline__ bool nll_position(const NllArgs& a, int64_t p, float& w, int64_t& off) {
-    const int64_t y = nll_label(a.labels, p, a.lbytes);
+    const int64_t y = load_label(a.labels, p, a.lbytes);
     if (y == a.ignore || y < 0 || y >= a.C) return false;
     const int64_t n = p / a.inner, i = p - n * a.inner;
     off = (n * a.C + y) * a.inner + i;

@@ -1,10 +1,11 @@
-// rowops.hip -- HBM-bound row kernels for gfx950: Softmax fwd/bwd, RMSNorm fwd/bwd (+dw/db),
-// fused CrossEntropy fwd+bwd, column sums (Linear db).
+// rowops.hip -- HBM-bound row kernels for gfx950: Softmax, LogSoftmax and the attention-score (masked) softmax fwd/bwd, the
+// LogSoftmax + NLLLoss backward fold, RMSNorm and LayerNorm fwd/bwd (+dw/db), fused CrossEntropy fwd+bwd, the two one-launch
+// head kernels (Linear + CrossEntropy, BatchNorm2d + Linear + Sigmoid + MSE), column sums (Linear db).
 //
 // Shape of every row kernel: a row (the reduction axis) is owned by TPR threads -- one wave64
 // (TPR=64, rows <= 1024 wide; a 256-thread block carries 4 rows) or a whole block (TPR=256 / 1024)
-// -- and is read ONCE into registers (NV float4 per thread = 16-B coalesced loads), reduced with
-// width-64 __shfl_xor (+ one LDS hop across waves), transformed and written once.  That is the
+// -- and is read ONCE into registers (NV float4 per thread = 16-B coalesced loads), reduced across
+// the wave on DPP (wave_sum / wave_max, common.h; + one LDS hop across waves), transformed and written once.  That is the
 // algorithmic traffic of SURVEY 8(d): 8 B/elem forward, 12 B/elem backward, 8 B/elem fused CE.
 // Rows wider than 16384 floats (or with a non-unit stride) take a looped fallback.
 #include <math.h>
@@ -118,8 +119,32 @@ constexpr int row_rpb(int tpr) { return tpr >= 256 ? 1 : 256 / tpr; }
     (void)red;
 
 // =================================================================================================
-// Softmax   (neunet/nn/activations.py:448-459 fwd, 437-446 bwd)
+// Softmax, LogSoftmax   (neunet/nn/activations.py:448-459 fwd, 437-446 bwd; 476-489 fwd, 466-471 bwd)
 // =================================================================================================
+// One body per layout (register rows, strided, looped) and direction, except the forward register rows; the two families differ in
+// the six expressions of their Op.
+// Forward: m = max x, v = keep(x, m), k = norm(sum term(v)), y = out(v, k); the row stays in registers between the passes.
+// Backward: s = sum dot(dy, y), dx = dx(dy, y, s).  A -inf entry among finite ones gives 0 / -inf there and finite values elsewhere;
+// LogSoftmax's sum is >= 1 (the maximum's own term), so its log is taken of a number in [1, cols].
+struct SoftmaxOp {      // y = exp(x - m) / sum exp(x - m);  dx = (dy - sum dy y) y
+    __device__ __forceinline__ static float keep(float x, float m) { return exp_fast_(x - m); }  // exp(-inf) = 0 for the padding lanes
+    __device__ __forceinline__ static float term(float v) { return v; }
+    __device__ __forceinline__ static float norm(float s) { return 1.0f / s; }
+    __device__ __forceinline__ static float out(float v, float k) { return v * k; }
+    __device__ __forceinline__ static float dot(float g, float y) { return g * y; }
+    __device__ __forceinline__ static float dx(float g, float y, float s) { return (g - s) * y; }
+};
+struct LogSoftmaxOp {   // y = (x - m) - log sum exp(x - m);  dx = dy - exp(y) sum dy
+    __device__ __forceinline__ static float keep(float x, float m) { return x - m; }
+    __device__ __forceinline__ static float term(float v) { return exp_fast_(v); }
+    __device__ __forceinline__ static float norm(float s) { return logf(s); }
+    __device__ __forceinline__ static float out(float v, float k) { return v - k; }
+    __device__ __forceinline__ static float dot(float g, float) { return g; }
+    __device__ __forceinline__ static float dx(float g, float y, float s) { return fmaf(-exp_fast_(y), s, g); }
+};
+
+// The two forward register kernels stay written out: on the shared body one timing row of each (8192 x 4096, 8192 x 1024) lay above
+// the parent build's own spread (EXPERIMENTS 5.32).  They are the forward above with the Op's expressions in place.
 template <int TPR, int NV, bool VEC>
 __global__ __launch_bounds__(row_block(TPR)) void softmax_fwd_rows(
     float* __restrict__ out, const float* __restrict__ in, int64_t rows, int64_t cols, int nt) {
@@ -142,28 +167,128 @@ __global__ __launch_bounds__(row_block(TPR)) void softmax_fwd_rows(
     for (int e = 0; e < r.NE; ++e) r.x[e] *= inv;
     r.store(out + row * cols, cols, t);
 }
-
 template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__(row_block(TPR)) void softmax_bwd_rows(
-    float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y, int64_t rows,
-    int64_t cols, int nt) {
+__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_fwd_rows(
+    float* __restrict__ out, const float* __restrict__ in, int64_t rows, int64_t cols, int nt) {
+    ROW_PROLOGUE(TPR)
+    RowTile<TPR, NV, VEC> r;
+    r.load(in + row * cols, cols, t, -INFINITY, nt);
+    float m = r.x[0];
+#pragma unroll
+    for (int e = 1; e < r.NE; ++e) m = fmaxf(m, r.x[e]);
+    m = row_max<TPR>(m, red);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) {
+        r.x[e] -= m;
+        s += exp_fast_(r.x[e]);  // exp(-inf) = 0 for the padding lanes
+    }
+    s = row_sum<TPR>(s, red);
+    const float lse = logf(s);
+#pragma unroll
+    for (int e = 0; e < r.NE; ++e) r.x[e] -= lse;
+    r.store(out + row * cols, cols, t);
+}
+
+template <class Op, int TPR, int NV, bool VEC>
+__device__ __forceinline__ void slice_bwd_rows(float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y,
+                                               int64_t rows, int64_t cols, int nt) {
     ROW_PROLOGUE(TPR)
     RowTile<TPR, NV, VEC> g, f;
     g.load(dy + row * cols, cols, t, 0.f, nt);
     f.load(y + row * cols, cols, t, 0.f, nt);
     float s = 0.f;
 #pragma unroll
-    for (int e = 0; e < g.NE; ++e) s += g.x[e] * f.x[e];
+    for (int e = 0; e < g.NE; ++e) s += Op::dot(g.x[e], f.x[e]);
     s = row_sum<TPR>(s, red);
 #pragma unroll
-    for (int e = 0; e < g.NE; ++e) g.x[e] = (g.x[e] - s) * f.x[e];
+    for (int e = 0; e < g.NE; ++e) g.x[e] = Op::dx(g.x[e], f.x[e], s);
     g.store(dx + row * cols, cols, t);
 }
+// Fallback: arbitrary slice length / stride.  One thread per slice when stride > 1 (adjacent slices
+// are adjacent in memory -> coalesced across threads); one block per slice when stride == 1.
+template <class Op>
+__device__ __forceinline__ void slice_fwd_strided(float* __restrict__ out, const float* __restrict__ in, int64_t num_slices, int64_t n,
+                                                  int64_t stride) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= num_slices) return;
+    const int64_t base = (s / stride) * n * stride + (s % stride);
+    float m = -INFINITY;
+    for (int64_t i = 0; i < n; ++i) m = fmaxf(m, in[base + i * stride]);
+    float d = 0.f;
+    for (int64_t i = 0; i < n; ++i) d += Op::term(Op::keep(in[base + i * stride], m));
+    const float k = Op::norm(d);
+    for (int64_t i = 0; i < n; ++i) out[base + i * stride] = Op::out(Op::keep(in[base + i * stride], m), k);
+}
+template <class Op>
+__device__ __forceinline__ void slice_bwd_strided(float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y,
+                                                  int64_t num_slices, int64_t n, int64_t stride) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= num_slices) return;
+    const int64_t base = (s / stride) * n * stride + (s % stride);
+    float d = 0.f;
+    for (int64_t i = 0; i < n; ++i) d += Op::dot(dy[base + i * stride], y[base + i * stride]);
+    for (int64_t i = 0; i < n; ++i) dx[base + i * stride] = Op::dx(dy[base + i * stride], y[base + i * stride], d);
+}
+template <class Op>
+__device__ __forceinline__ void slice_fwd_looped(float* __restrict__ out, const float* __restrict__ in, int64_t n) {
+    __shared__ float red[4];
+    const float* x = in + (int64_t)blockIdx.x * n;
+    float* o = out + (int64_t)blockIdx.x * n;
+    float m = -INFINITY;
+    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
+    m = block_max<4>(m, red);
+    float d = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) d += Op::term(Op::keep(x[i], m));
+    d = block_sum<4>(d, red);
+    const float k = Op::norm(d);
+    for (int64_t i = threadIdx.x; i < n; i += 256) o[i] = Op::out(Op::keep(x[i], m), k);
+}
+template <class Op>
+__device__ __forceinline__ void slice_bwd_looped(float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y,
+                                                 int64_t n) {
+    __shared__ float red[4];
+    const int64_t b = (int64_t)blockIdx.x * n;
+    float d = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) d += Op::dot(dy[b + i], y[b + i]);
+    d = block_sum<4>(d, red);
+    for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = Op::dx(dy[b + i], y[b + i], d);
+}
+
+// The other kernels of a family: the names the profiles and tools key on, each one call of its body.
+#define SLICE_KERNELS(name, Op)                                                                                                     \
+    template <int TPR, int NV, bool VEC>                                                                                            \
+    __global__ __launch_bounds__(row_block(TPR)) void name##_bwd_rows(float* __restrict__ dx, const float* __restrict__ dy,         \
+                                                                      const float* __restrict__ y, int64_t rows, int64_t cols,      \
+                                                                      int nt) {                                                     \
+        slice_bwd_rows<Op, TPR, NV, VEC>(dx, dy, y, rows, cols, nt);                                                                \
+    }                                                                                                                               \
+    __global__ __launch_bounds__(256) void name##_fwd_strided(float* __restrict__ out, const float* __restrict__ in,                \
+                                                              int64_t num_slices, int64_t n, int64_t stride) {                      \
+        slice_fwd_strided<Op>(out, in, num_slices, n, stride);                                                                      \
+    }                                                                                                                               \
+    __global__ __launch_bounds__(256) void name##_bwd_strided(float* __restrict__ dx, const float* __restrict__ dy,                 \
+                                                              const float* __restrict__ y, int64_t num_slices, int64_t n,           \
+                                                              int64_t stride) {                                                     \
+        slice_bwd_strided<Op>(dx, dy, y, num_slices, n, stride);                                                                    \
+    }                                                                                                                               \
+    __global__ __launch_bounds__(256) void name##_fwd_looped(float* __restrict__ out, const float* __restrict__ in, int64_t n) {    \
+        slice_fwd_looped<Op>(out, in, n);                                                                                           \
+    }                                                                                                                               \
+    __global__ __launch_bounds__(256) void name##_bwd_looped(float* __restrict__ dx, const float* __restrict__ dy,                  \
+                                                             const float* __restrict__ y, int64_t n) {                              \
+        slice_bwd_looped<Op>(dx, dy, y, n);                                                                                         \
+    }
+SLICE_KERNELS(softmax, SoftmaxOp)
+SLICE_KERNELS(logsoftmax, LogSoftmaxOp)
+#undef SLICE_KERNELS
 
 // Attention-score softmax with the scale and the mask fused in (examples/gpt.ipynb cell 2:
 // scores = QK^T / sqrt(d_model); scores = where(mask == 0, -1e9, scores); attn = Softmax(-1)(scores)).
 // Row r <-> (b, h, i); column j is masked when key j of batch b is padding (key_valid[b,j] == 0) or, if
 // `causal`, j > i + (cols - Tq).  Masked scores are REPLACED by -1e9 (not -inf), exactly like the reference.
+// The four masked kernels stay written out: they start from m = -inf over transformed elements, run without `nt`, may work in place
+// and loop at 1024 threads, so folding them into the bodies above would put those differences into the shared code (EXPERIMENTS 5.32).
 template <int TPR, int NV, bool VEC>
 __global__ __launch_bounds__(row_block(TPR)) void softmax_masked_fwd_rows(
     float* out, const float* in, const int32_t* __restrict__ key_valid,  // out may alias in
@@ -226,60 +351,6 @@ __global__ __launch_bounds__(row_block(TPR)) void softmax_masked_bwd_rows(
         g.x[e] = masked ? 0.f : (g.x[e] - s) * f.x[e] * scale;
     }
     g.store(dx + row * cols, cols, t);
-}
-
-// Fallback: arbitrary slice length / stride.  One thread per slice when stride > 1 (adjacent slices
-// are adjacent in memory -> coalesced across threads); one block per slice when stride == 1.
-__global__ __launch_bounds__(256) void softmax_fwd_strided(float* __restrict__ out,
-                                                           const float* __restrict__ in,
-                                                           int64_t num_slices, int64_t n,
-                                                           int64_t stride) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= num_slices) return;
-    const int64_t base = (s / stride) * n * stride + (s % stride);
-    float m = -INFINITY;
-    for (int64_t i = 0; i < n; ++i) m = fmaxf(m, in[base + i * stride]);
-    float d = 0.f;
-    for (int64_t i = 0; i < n; ++i) d += exp_fast_(in[base + i * stride] - m);
-    const float inv = 1.0f / d;
-    for (int64_t i = 0; i < n; ++i) out[base + i * stride] = exp_fast_(in[base + i * stride] - m) * inv;
-}
-__global__ __launch_bounds__(256) void softmax_bwd_strided(float* __restrict__ dx,
-                                                           const float* __restrict__ dy,
-                                                           const float* __restrict__ y,
-                                                           int64_t num_slices, int64_t n,
-                                                           int64_t stride) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= num_slices) return;
-    const int64_t base = (s / stride) * n * stride + (s % stride);
-    float d = 0.f;
-    for (int64_t i = 0; i < n; ++i) d += dy[base + i * stride] * y[base + i * stride];
-    for (int64_t i = 0; i < n; ++i)
-        dx[base + i * stride] = (dy[base + i * stride] - d) * y[base + i * stride];
-}
-__global__ __launch_bounds__(256) void softmax_fwd_looped(float* __restrict__ out,
-                                                          const float* __restrict__ in, int64_t n) {
-    __shared__ float red[4];
-    const float* x = in + (int64_t)blockIdx.x * n;
-    float* o = out + (int64_t)blockIdx.x * n;
-    float m = -INFINITY;
-    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
-    m = block_max<4>(m, red);
-    float d = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) d += exp_fast_(x[i] - m);
-    d = block_sum<4>(d, red);
-    const float inv = 1.0f / d;
-    for (int64_t i = threadIdx.x; i < n; i += 256) o[i] = exp_fast_(x[i] - m) * inv;
-}
-__global__ __launch_bounds__(256) void softmax_bwd_looped(float* __restrict__ dx,
-                                                          const float* __restrict__ dy,
-                                                          const float* __restrict__ y, int64_t n) {
-    __shared__ float red[4];
-    const int64_t b = (int64_t)blockIdx.x * n;
-    float d = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) d += dy[b + i] * y[b + i];
-    d = block_sum<4>(d, red);
-    for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = (dy[b + i] - d) * y[b + i];
 }
 
 // =================================================================================================
@@ -864,12 +935,6 @@ struct CeArgs {
     int count_in_kernel;        // 1: every block derives the 'mean' denominator from the labels
     int nt;                     // 1: streaming loads of the logits (row_streaming())
 };
-
-__device__ __forceinline__ int64_t load_label(const void* labels, int64_t i, int lbytes) {
-    if (lbytes == 4) return reinterpret_cast<const int32_t*>(labels)[i];
-    if (lbytes == 8) return reinterpret_cast<const int64_t*>(labels)[i];
-    return reinterpret_cast<const int16_t*>(labels)[i];
-}
 
 template <int NW>
 __device__ __forceinline__ int block_sum_int(int v, int* red) {
@@ -1619,94 +1684,7 @@ __global__ __launch_bounds__(1024) void softmax_masked_bwd_looped(float* dx, con
     }
 }
 
-// =================================================================================================
-// LogSoftmax   (neunet/nn/activations.py:476-489 fwd, 466-471 bwd), the layouts of Softmax above
-// =================================================================================================
-// y = x - m - log(sum exp(x - m)): the row stays in registers between the passes.  The sum is >= 1 (the maximum's own term), so the
-// log is taken of a number in [1, cols].  A -inf entry among finite ones gives -inf there and finite values elsewhere.
-template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_fwd_rows(
-    float* __restrict__ out, const float* __restrict__ in, int64_t rows, int64_t cols, int nt) {
-    ROW_PROLOGUE(TPR)
-    RowTile<TPR, NV, VEC> r;
-    r.load(in + row * cols, cols, t, -INFINITY, nt);
-    float m = r.x[0];
-#pragma unroll
-    for (int e = 1; e < r.NE; ++e) m = fmaxf(m, r.x[e]);
-    m = row_max<TPR>(m, red);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < r.NE; ++e) {
-        r.x[e] -= m;
-        s += exp_fast_(r.x[e]);  // exp(-inf) = 0 for the padding lanes
-    }
-    s = row_sum<TPR>(s, red);
-    const float lse = logf(s);
-#pragma unroll
-    for (int e = 0; e < r.NE; ++e) r.x[e] -= lse;
-    r.store(out + row * cols, cols, t);
-}
-// dx = dy - exp(y) * sum_c dy
-template <int TPR, int NV, bool VEC>
-__global__ __launch_bounds__(row_block(TPR)) void logsoftmax_bwd_rows(
-    float* __restrict__ dx, const float* __restrict__ dy, const float* __restrict__ y, int64_t rows,
-    int64_t cols, int nt) {
-    ROW_PROLOGUE(TPR)
-    RowTile<TPR, NV, VEC> g, f;
-    g.load(dy + row * cols, cols, t, 0.f, nt);
-    f.load(y + row * cols, cols, t, 0.f, nt);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < g.NE; ++e) s += g.x[e];
-    s = row_sum<TPR>(s, red);
-#pragma unroll
-    for (int e = 0; e < g.NE; ++e) g.x[e] = fmaf(-exp_fast_(f.x[e]), s, g.x[e]);
-    g.store(dx + row * cols, cols, t);
-}
-__global__ __launch_bounds__(256) void logsoftmax_fwd_strided(float* __restrict__ out, const float* __restrict__ in,
-                                                              int64_t num_slices, int64_t n, int64_t stride) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= num_slices) return;
-    const int64_t base = (s / stride) * n * stride + (s % stride);
-    float m = -INFINITY;
-    for (int64_t i = 0; i < n; ++i) m = fmaxf(m, in[base + i * stride]);
-    float d = 0.f;
-    for (int64_t i = 0; i < n; ++i) d += exp_fast_(in[base + i * stride] - m);
-    const float lse = logf(d);
-    for (int64_t i = 0; i < n; ++i) out[base + i * stride] = in[base + i * stride] - m - lse;
-}
-__global__ __launch_bounds__(256) void logsoftmax_bwd_strided(float* __restrict__ dx, const float* __restrict__ dy,
-                                                              const float* __restrict__ y, int64_t num_slices, int64_t n,
-                                                              int64_t stride) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= num_slices) return;
-    const int64_t base = (s / stride) * n * stride + (s % stride);
-    float d = 0.f;
-    for (int64_t i = 0; i < n; ++i) d += dy[base + i * stride];
-    for (int64_t i = 0; i < n; ++i) dx[base + i * stride] = fmaf(-exp_fast_(y[base + i * stride]), d, dy[base + i * stride]);
-}
-__global__ __launch_bounds__(256) void logsoftmax_fwd_looped(float* __restrict__ out, const float* __restrict__ in, int64_t n) {
-    __shared__ float red[4];
-    const float* x = in + (int64_t)blockIdx.x * n;
-    float* o = out + (int64_t)blockIdx.x * n;
-    float m = -INFINITY;
-    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
-    m = block_max<4>(m, red);
-    float d = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) d += exp_fast_(x[i] - m);
-    d = block_sum<4>(d, red);
-    const float lse = logf(d);
-    for (int64_t i = threadIdx.x; i < n; i += 256) o[i] = x[i] - m - lse;
-}
-__global__ __launch_bounds__(256) void logsoftmax_bwd_looped(float* __restrict__ dx, const float* __restrict__ dy,
-                                                             const float* __restrict__ y, int64_t n) {
-    __shared__ float red[4];
-    const int64_t b = (int64_t)blockIdx.x * n;
-    float d = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) d += dy[b + i];
-    d = block_sum<4>(d, red);
-    for (int64_t i = threadIdx.x; i < n; i += 256) dx[b + i] = fmaf(-exp_fast_(y[b + i]), d, dy[b + i]);
-}
+// ---- LogSoftmax + NLLLoss --------------------------------------------------------------------------------------------
 // NLLLoss(LogSoftmax(x)) backward in one pass: dx[n, c] = g_n ([c == y_n] - exp(Y[n, c])) u.  g_n = pos_grad[n] is the one value per
 // row the NLL entry wrote (0: the row is ignored, or its label is out of range -- zeros, and the label is not looked at), u the scalar
 // upstream gradient (a device word another kernel wrote: an agent-scope load).
@@ -1903,98 +1881,76 @@ static int norm_backward(const float* dY, const float* X, const float* weight, c
     return colsum_tall(part_db, dB, nullptr, nullptr, nblk, cols, vec, st);
 }
 
+// ---- the host side of the four Softmax / LogSoftmax entries -----------------------------------------------------------------
+// What an entry hands to slice_op (its `Entry`): its name for the messages, its launch-check name and its three kernels.
+struct SoftmaxForward {
+    static constexpr const char *entry = "nnhipSoftmaxForward", *launch_name = "softmax_forward";
+    template <int TPR, int NV, bool VEC> static auto rows() { return softmax_fwd_rows<TPR, NV, VEC>; }
+    static auto strided() { return softmax_fwd_strided; }
+    static auto looped() { return softmax_fwd_looped; }
+};
+struct SoftmaxBackward {
+    static constexpr const char *entry = "nnhipSoftmaxBackward", *launch_name = "softmax_backward";
+    template <int TPR, int NV, bool VEC> static auto rows() { return softmax_bwd_rows<TPR, NV, VEC>; }
+    static auto strided() { return softmax_bwd_strided; }
+    static auto looped() { return softmax_bwd_looped; }
+};
+struct LogSoftmaxForward {
+    static constexpr const char *entry = "nnhipLogSoftmaxForward", *launch_name = "logsoftmax_forward";
+    template <int TPR, int NV, bool VEC> static auto rows() { return logsoftmax_fwd_rows<TPR, NV, VEC>; }
+    static auto strided() { return logsoftmax_fwd_strided; }
+    static auto looped() { return logsoftmax_fwd_looped; }
+};
+struct LogSoftmaxBackward {
+    static constexpr const char *entry = "nnhipLogSoftmaxBackward", *launch_name = "logsoftmax_backward";
+    template <int TPR, int NV, bool VEC> static auto rows() { return logsoftmax_bwd_rows<TPR, NV, VEC>; }
+    static auto strided() { return logsoftmax_bwd_strided; }
+    static auto looped() { return logsoftmax_bwd_looped; }
+};
+
+// p...: the entry's arrays in its kernels' order, (out, in) or (dX, dY, Y).  Strided slices take the thread-per-slice kernel, rows
+// beyond the register tile the looped one, everything else its tier of the register kernel.
+template <class Entry, class... P>
+static int slice_op(int64_t num_slices, int64_t slice_size, int64_t stride, nnhipStream_t s, P*... p) {
+    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "%s: negative size", Entry::entry);
+    if (num_slices == 0 || slice_size == 0) return 0;
+    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "%s: stride must be >= 1", Entry::entry);
+    NNHIP_CHECK_ARG((p && ...), NNHIP_EINVAL, "%s: null pointer", Entry::entry);
+    hipStream_t st = (hipStream_t)s;
+    if (stride != 1) {
+        hipLaunchKernelGGL(Entry::strided(), dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st, p..., num_slices, slice_size, stride);
+    } else if (slice_size > kMaxRegRow) {
+        hipLaunchKernelGGL(Entry::looped(), dim3((unsigned)num_slices), dim3(256), 0, st, p..., slice_size);
+    } else {
+        const bool vec = (aligned16(p) && ...) && slice_size % 4 == 0;
+        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
+            row_launch<tpr>(Entry::template rows<tpr, nv, v>(), num_slices, st, p..., num_slices, slice_size,
+                            row_streaming(num_slices, slice_size, slice_size));
+        });
+    }
+    NNHIP_LAUNCH_CHECK(Entry::launch_name);
+    return 0;
+}
+
 }  // namespace nnhip
 
 using namespace nnhip;
 
-// ---- Softmax ------------------------------------------------------------------------------------
-extern "C" int nnhipSoftmaxForward(float* out, const float* in, int64_t num_slices,
-                                   int64_t slice_size, int64_t stride, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipSoftmaxForward: negative size");
-    if (num_slices == 0 || slice_size == 0) return 0;
-    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipSoftmaxForward: stride must be >= 1");
-    NNHIP_CHECK_ARG(out && in, NNHIP_EINVAL, "nnhipSoftmaxForward: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (stride != 1) {
-        hipLaunchKernelGGL(softmax_fwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
-                           out, in, num_slices, slice_size, stride);
-    } else if (slice_size > kMaxRegRow) {
-        hipLaunchKernelGGL(softmax_fwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, out, in, slice_size);
-    } else {
-        const bool vec = aligned16(out) && aligned16(in) && slice_size % 4 == 0;
-        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
-            row_launch<tpr>(softmax_fwd_rows<tpr, nv, v>, num_slices, st, out, in, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
-        });
-    }
-    NNHIP_LAUNCH_CHECK("softmax_forward");
-    return 0;
+// ---- Softmax, LogSoftmax ------------------------------------------------------------------------------------------------
+extern "C" int nnhipSoftmaxForward(float* out, const float* in, int64_t num_slices, int64_t slice_size, int64_t stride, nnhipStream_t s) {
+    return slice_op<SoftmaxForward>(num_slices, slice_size, stride, s, out, in);
 }
-
-extern "C" int nnhipSoftmaxBackward(float* dX, const float* dY, const float* Y, int64_t num_slices,
-                                    int64_t slice_size, int64_t stride, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipSoftmaxBackward: negative size");
-    if (num_slices == 0 || slice_size == 0) return 0;
-    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipSoftmaxBackward: stride must be >= 1");
-    NNHIP_CHECK_ARG(dX && dY && Y, NNHIP_EINVAL, "nnhipSoftmaxBackward: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (stride != 1) {
-        hipLaunchKernelGGL(softmax_bwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
-                           dX, dY, Y, num_slices, slice_size, stride);
-    } else if (slice_size > kMaxRegRow) {
-        hipLaunchKernelGGL(softmax_bwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, dX, dY, Y, slice_size);
-    } else {
-        const bool vec = aligned16(dX) && aligned16(dY) && aligned16(Y) && slice_size % 4 == 0;
-        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
-            row_launch<tpr>(softmax_bwd_rows<tpr, nv, v>, num_slices, st, dX, dY, Y, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
-        });
-    }
-    NNHIP_LAUNCH_CHECK("softmax_backward");
-    return 0;
+extern "C" int nnhipSoftmaxBackward(float* dX, const float* dY, const float* Y, int64_t num_slices, int64_t slice_size, int64_t stride,
+                                    nnhipStream_t s) {
+    return slice_op<SoftmaxBackward>(num_slices, slice_size, stride, s, dX, dY, Y);
 }
-
-// ---- LogSoftmax -----------------------------------------------------------------------------------
 extern "C" int nnhipLogSoftmaxForward(float* out, const float* in, int64_t num_slices, int64_t slice_size, int64_t stride,
                                       nnhipStream_t s) {
-    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipLogSoftmaxForward: negative size");
-    if (num_slices == 0 || slice_size == 0) return 0;
-    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipLogSoftmaxForward: stride must be >= 1");
-    NNHIP_CHECK_ARG(out && in, NNHIP_EINVAL, "nnhipLogSoftmaxForward: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (stride != 1) {
-        hipLaunchKernelGGL(logsoftmax_fwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
-                           out, in, num_slices, slice_size, stride);
-    } else if (slice_size > kMaxRegRow) {
-        hipLaunchKernelGGL(logsoftmax_fwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, out, in, slice_size);
-    } else {
-        const bool vec = aligned16(out) && aligned16(in) && slice_size % 4 == 0;
-        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
-            row_launch<tpr>(logsoftmax_fwd_rows<tpr, nv, v>, num_slices, st, out, in, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
-        });
-    }
-    NNHIP_LAUNCH_CHECK("logsoftmax_forward");
-    return 0;
+    return slice_op<LogSoftmaxForward>(num_slices, slice_size, stride, s, out, in);
 }
-
 extern "C" int nnhipLogSoftmaxBackward(float* dX, const float* dY, const float* Y, int64_t num_slices, int64_t slice_size,
                                        int64_t stride, nnhipStream_t s) {
-    NNHIP_CHECK_ARG(num_slices >= 0 && slice_size >= 0, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: negative size");
-    if (num_slices == 0 || slice_size == 0) return 0;
-    NNHIP_CHECK_ARG(stride >= 1, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: stride must be >= 1");
-    NNHIP_CHECK_ARG(dX && dY && Y, NNHIP_EINVAL, "nnhipLogSoftmaxBackward: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (stride != 1) {
-        hipLaunchKernelGGL(logsoftmax_bwd_strided, dim3((unsigned)ceil_div(num_slices, 256)), dim3(256), 0, st,
-                           dX, dY, Y, num_slices, slice_size, stride);
-    } else if (slice_size > kMaxRegRow) {
-        hipLaunchKernelGGL(logsoftmax_bwd_looped, dim3((unsigned)num_slices), dim3(256), 0, st, dX, dY, Y, slice_size);
-    } else {
-        const bool vec = aligned16(dX) && aligned16(dY) && aligned16(Y) && slice_size % 4 == 0;
-        row_tier(slice_size, vec, [&](auto tpr, auto nv, auto v) {
-            row_launch<tpr>(logsoftmax_bwd_rows<tpr, nv, v>, num_slices, st, dX, dY, Y, num_slices, slice_size, row_streaming(num_slices, slice_size, slice_size));
-        });
-    }
-    NNHIP_LAUNCH_CHECK("logsoftmax_backward");
-    return 0;
+    return slice_op<LogSoftmaxBackward>(num_slices, slice_size, stride, s, dX, dY, Y);
 }
 
 extern "C" int nnhipLogSoftmaxNLLBackward(float* dX, const float* Y, const void* labels, int32_t label_bytes, const float* pos_grad,

@@ -251,7 +251,7 @@ class HIPFusedSwishAndMul(Module):
         return _HIPFusedSwishAndMulTensor(out, [x, self.beta], "fused_swish_and_mul", device=x.device)
 
 
-# ---------------------------------------------------------------------------------------- Softmax
+# ---------------------------------------------------------------------------- Softmax, LogSoftmax
 def _slices(a, dim):
     dim = dim % a.ndim
     slice_size = a.shape[dim]
@@ -260,38 +260,64 @@ def _slices(a, dim):
     return num_slices, slice_size, stride
 
 
-def hip_softmax_forward(x, o, dim: int):
-    """cuda_softmax_forward (softmax.py:52-94): arbitrary axis through (num_slices, slice_size, stride)."""
+def _slice_forward(entry, x, o, dim):
+    """Both families' forward: arbitrary axis through (num_slices, slice_size, stride)."""
     _check_arrays(x, o)
     if x.shape != o.shape:
         raise ValueError("Input and output shapes must match")
     x = contiguous(x)
     n, s, st = _slices(x, dim)
-    call_hip_function("nnhipSoftmaxForward", o, x, n, s, st, get_current_stream_ptr())
+    call_hip_function(entry, o, x, n, s, st, get_current_stream_ptr())
     return o
+
+
+def _slice_backward(entry, what, grad_x, grad, f_x, dim):
+    _check_arrays(grad_x, grad, f_x)
+    if grad_x.shape != grad.shape or grad_x.shape != f_x.shape:
+        raise ValueError(f"Input, output gradients and {what} shapes must match")
+    grad, f_x = contiguous(grad), contiguous(f_x)
+    n, s, st = _slices(f_x, dim)
+    call_hip_function(entry, grad_x, grad, f_x, n, s, st, get_current_stream_ptr())
+    return grad_x
+
+
+def hip_softmax_forward(x, o, dim: int):
+    """cuda_softmax_forward (softmax.py:52-94)."""
+    return _slice_forward("nnhipSoftmaxForward", x, o, dim)
 
 
 def hip_softmax_backward(grad_x, grad, f_x, dim: int):
     """cuda_softmax_backward (softmax.py:96-136)."""
-    _check_arrays(grad_x, grad, f_x)
-    if grad_x.shape != grad.shape or grad_x.shape != f_x.shape:
-        raise ValueError("Input, output gradients and softmax shapes must match")
-    grad, f_x = contiguous(grad), contiguous(f_x)
-    n, s, st = _slices(f_x, dim)
-    call_hip_function("nnhipSoftmaxBackward", grad_x, grad, f_x, n, s, st, get_current_stream_ptr())
-    return grad_x
+    return _slice_backward("nnhipSoftmaxBackward", "softmax", grad_x, grad, f_x, dim)
 
 
-class _HIPSoftmaxTensor(Tensor):
+def hip_logsoftmax_forward(x, o, dim: int):
+    """neunet/nn/activations.py:485-488 -> nnhipLogSoftmaxForward."""
+    return _slice_forward("nnhipLogSoftmaxForward", x, o, dim)
+
+
+def hip_logsoftmax_backward(grad_x, grad, f_x, dim: int):
+    """neunet/nn/activations.py:466-471: grad - exp(f_x) * grad.sum(axis) -> nnhipLogSoftmaxBackward."""
+    return _slice_backward("nnhipLogSoftmaxBackward", "log-softmax", grad_x, grad, f_x, dim)
+
+
+class _HIPSliceTensor(Tensor):
+    """args = [input, output, axis].  `_backward_name`: the family's module-level helper, looked up when the gradient runs."""
+
     def __init__(self, data, args, op, device):
         super().__init__(data, args, op, device=device, _nocopy=True)
+        name = self._backward_name
 
         def grad_fn(t: Tensor, f_x, axis, grad):
-            grad_x = t.xp.empty_like(t.data)
-            hip_softmax_backward(grad_x, grad, f_x, axis)
+            grad_x = t.xp.empty_like(f_x)
+            globals()[name](grad_x, grad, f_x, axis)
             t.apply_grad(grad_x)
 
         self.grad_fn = grad_fn
+
+
+class _HIPSoftmaxTensor(_HIPSliceTensor):
+    _backward_name = "hip_softmax_backward"
 
 
 class HIPSoftmax(Module):
@@ -306,41 +332,10 @@ class HIPSoftmax(Module):
         return _HIPSoftmaxTensor(f_x, [x, f_x, self.axis], "softmax", device=x.device)
 
 
-# ------------------------------------------------------------------------------------- LogSoftmax
-def hip_logsoftmax_forward(x, o, dim: int):
-    """neunet/nn/activations.py:485-488 -> nnhipLogSoftmaxForward: arbitrary axis through (num_slices, slice_size, stride)."""
-    _check_arrays(x, o)
-    if x.shape != o.shape:
-        raise ValueError("Input and output shapes must match")
-    x = contiguous(x)
-    n, s, st = _slices(x, dim)
-    call_hip_function("nnhipLogSoftmaxForward", o, x, n, s, st, get_current_stream_ptr())
-    return o
+class _HIPLogSoftmaxTensor(_HIPSliceTensor):
+    """HIPNLLLoss looks at this node's args to fold its backward into this node's (losses.py)."""
 
-
-def hip_logsoftmax_backward(grad_x, grad, f_x, dim: int):
-    """neunet/nn/activations.py:466-471: grad - exp(f_x) * grad.sum(axis) -> nnhipLogSoftmaxBackward."""
-    _check_arrays(grad_x, grad, f_x)
-    if grad_x.shape != grad.shape or grad_x.shape != f_x.shape:
-        raise ValueError("Input, output gradients and log-softmax shapes must match")
-    grad, f_x = contiguous(grad), contiguous(f_x)
-    n, s, st = _slices(f_x, dim)
-    call_hip_function("nnhipLogSoftmaxBackward", grad_x, grad, f_x, n, s, st, get_current_stream_ptr())
-    return grad_x
-
-
-class _HIPLogSoftmaxTensor(Tensor):
-    """args = [input, output, axis]: HIPNLLLoss looks at them to fold its backward into this node's (losses.py)."""
-
-    def __init__(self, data, args, op, device):
-        super().__init__(data, args, op, device=device, _nocopy=True)
-
-        def grad_fn(t: Tensor, f_x, axis, grad):
-            grad_x = t.xp.empty_like(f_x)
-            hip_logsoftmax_backward(grad_x, grad, f_x, axis)
-            t.apply_grad(grad_x)
-
-        self.grad_fn = grad_fn
+    _backward_name = "hip_logsoftmax_backward"
 
 
 class HIPLogSoftmax(Module):
