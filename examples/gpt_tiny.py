@@ -159,12 +159,16 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seq", type=int, default=64)
     ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM",
+                    help="clip the gradients to this global L2 norm inside optimizer.step() (default: no clipping)")
     a = ap.parse_args()
     np.random.seed(0)
     model = build_gpt(a.vocab, a.d_model, a.heads, 4 * a.d_model, a.layers, pad_idx=0, max_len=a.seq + 1, dropout=a.dropout)
     opt = Adam(model.parameters(), lr=1e-3, betas=(0.9, 0.98), eps=1e-9)
+    opt.max_grad_norm = a.clip        # one extra launch per step leaves norm and clip factor on the device; the update divides by it
     loss_fn = nn.CrossEntropyLoss(ignore_index=0)
     for i, batch in enumerate(synthetic_batches(a.vocab, a.batch, a.seq, a.steps)):
         loss = train_step(model, opt, loss_fn, batch)
         if i % 20 == 0 or i == a.steps - 1:
-            print(f"step {i:4d}  loss {loss.item():.4f}", flush=True)
+            norm = "" if a.clip is None else f"  grad norm {opt.last_grad_norm.item():.4f}"     # the norm BEFORE clipping
+            print(f"step {i:4d}  loss {loss.item():.4f}{norm}", flush=True)

@@ -488,6 +488,39 @@ int nnhipOptimizerRuleMultiTensorStep(void* opt, int32_t rule, int32_t n_tensors
                                       float* const* s1, float* const* s2, const int64_t* sizes, double lr, double coef1,
                                       double coef2, double eps, int32_t step, float grad_scale, nnhipStream_t stream);
 
+/* ---- Gradient clipping by global norm (net-new exports, ABI 226; csrc/grad_norm.hip: the reference has no gradient clipping).
+ *   The norm of ALL gradient tensors in one launch, finished inside that launch (no float atomics: the same gradients give the same
+ *   bits; no memset, no host synchronisation: legal in a captured step), on a handle of nnhipCreateFusedOptimizer.  The result is the
+ *   one-float device word the update kernels already divide the gradient by (nnhipFusedOptimizerSetGradDivisor): clipping needs no
+ *   pass over the gradients.
+ *   words: 4 device floats.
+ *     out [0] = the norm of the EFFECTIVE gradient g * gs, gs = grad_scale / divisor_in[0] -- the factor the update kernels apply:
+ *               |gs| * sqrt(sum g^2) (NNHIP_NORM_L2; float32 sums per block, the blocks' sums added in double) or |gs| * max |g|
+ *               (NNHIP_NORM_INF; exact, and a NaN element gives NaN)
+ *     out [1] = the divisor an update must use = divisor_in[0] * max(1, (norm + 1e-6f) / max_norm): torch's clip_coef, clamped,
+ *               inverted (divisor_in == NULL counts as 1; equal to divisor_in[0] bit for bit when nothing is clipped; NaN when the
+ *               norm is NaN)
+ *     out [2] = 1.0f when the norm is NaN or inf, else 0.0f
+ *     in  [3] = max_norm for step == 0
+ *   g / sizes: HOST arrays of n_tensors DEVICE pointers / element counts, as nnhipFusedAdamWMultiTensorStep's; the plan (the handle's
+ *   second plan slot, so the update's plan stays cached) is re-uploaded only when it changed.  step >= 1: grad_scale and max_norm are
+ *   the arguments.  step == 0: device-driven stepping -- grad_scale comes from the handle's device state (nnhipFusedOptimizerSetStep /
+ *   SetHyper) and max_norm from words[3]; the two arguments are ignored.  The handle's bound divisor is not read: pass it as
+ *   divisor_in.  n_tensors == 0 or all sizes 0: one one-block launch writes norm 0, divisor = divisor_in[0] (or 1), flag 0.
+ *   NNHIP_EINVAL: NULL handle, NULL words, NULL table with n_tensors > 0, negative n_tensors / size / step, NULL tensor pointer with a
+ *   non-zero size, unknown norm_type, max_norm NaN or <= 0 at step >= 1, step == 0 without SetStep and SetHyper.  NNHIP_EALIGN: a
+ *   tensor, words or divisor pointer that is not 4-byte aligned.  NNHIP_ENOMEM: the handle's partials buffer (one float per block,
+ *   grow-only) would have to grow inside a stream capture -- run the step eagerly once first.  A refused call launches nothing. */
+enum { NNHIP_NORM_L2 = 0, NNHIP_NORM_INF = 1 };
+int nnhipGradNormMultiTensor(void* opt, int32_t n_tensors, const float* const* g, const int64_t* sizes, int32_t norm_type,
+                             double max_norm, const float* divisor_in_or_null, int32_t step, float grad_scale, float* words,
+                             nnhipStream_t stream);
+/* g[i] /= divisor_dev[0] for every tensor, in place, one launch, on the same plan slot: for callers that clip without one of the
+ * optimizers here or want to look at the clipped gradients.  A divisor of 1.0f leaves every bit as it is.  Status codes as above
+ * (NULL divisor_dev: NNHIP_EINVAL); n_tensors == 0 or all sizes 0: returns 0 without a launch. */
+int nnhipScaleMultiTensor(void* opt, int32_t n_tensors, float* const* g, const int64_t* sizes, const float* divisor_dev,
+                          nnhipStream_t stream);
+
 /* ---- a3/a4 Conv2d  (net-new exports; reference CPU: neunet/nn/layers/conv2d.py:297-355, 16-115)
  *   X [B,Cin,H,W], W [Cout,Cin,kh,kw], bias [Cout] or NULL, O [B,Cout,Ho,Wo]; NCHW fp32.
  *   pad = (up, down, left, right) as Conv2d.build resolves it (conv2d.py:237-243);

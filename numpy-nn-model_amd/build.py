@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "neunet_hip", "lib")
 LIB = os.path.join(LIBDIR, "libneunet_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "avgpool.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip", "tensor_ops.hip", "tensor_index.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "gemm_small.hip", "gemm_bf3.hip", "gemm_pst.hip", "elementwise.hip", "rowops.hip", "optim.hip", "optim_rules.hip", "grad_norm.hip", "linear.hip", "linear_gemv.hip", "conv2d.hip", "conv_mfma.hip", "conv_transpose.hip", "embedding.hip", "pool_norm.hip", "avgpool.hip", "batchnorm1d.hip", "losses_latent.hip", "attention.hip", "attention_sb.hip", "attention_decode.hip", "attention_cross_decode.hip", "comm.hip", "recurrent.hip", "recurrent_gru.hip", "sample.hip", "vector_quantize.hip", "tensor_ops.hip", "tensor_index.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "adam_device.h"), os.path.join(CSRC, "optim_rules_device.h"), os.path.join(CSRC, "gemm_small.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_tap.h"), os.path.join(CSRC, "attention.h"), os.path.join(CSRC, "attention_decode.h"), os.path.join(CSRC, "arg_order.h"), os.path.join(CSRC, "recurrent_common.h"), os.path.join(CSRC, "ew_map.h"), os.path.join(CSRC, "deferred_queue.h"), os.path.join(CSRC, "tensor_ops.h"),
            os.path.join(os.path.dirname(HERE), "include", "neunet_hip.h")]
 ARCH = "gfx950"
@@ -62,6 +62,8 @@ NO_SPILL = {"gemm.hip": (r"gemm_f32_kernelILi\d+ELb[01]ELb[01]ELb1E",),
             # the optimizer rules are nothing but streaming loads and stores, up to four rounds of a rule's streams in flight per
             # lane: a spill would put the loads' destinations in scratch
             "optim_rules.hip": (r"optim_rule_",),
+            # the gradient norm and the in-place scale: streaming loads (four in flight per lane) into four accumulators, nothing to spill
+            "grad_norm.hip": (r"grad_norm_", r"grad_scale_"),
             # AvgPool2d: window sums held in one or two registers next to streaming loads and stores, nothing to spill
             "avgpool.hip": (r"avgpool_",),
             # the tape's elementwise and structured reduction kernels are streaming loads (row-wave keeps a row of 16 values per lane

@@ -139,23 +139,33 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const unsigned char* _
 // staging buffers so the upload is asynchronous.
 struct FusedOptimizer {
     static constexpr int kRing = 4;
-    std::vector<unsigned char> last;  // last uploaded blob (host copy)
-    unsigned char* dev = nullptr;
-    size_t dev_cap = 0;
+    // One plan per slot (last uploaded blob: host copy, device copy): slot 0 is the update's, slot 1 the gradient norm's
+    // (grad_norm.hip) -- two launches per step on one handle would otherwise evict each other's "unchanged, no upload" cache.
+    static constexpr int kSlots = 2;
+    struct Plan {
+        std::vector<unsigned char> last;
+        unsigned char* dev = nullptr;
+        size_t dev_cap = 0;
+    } plan[kSlots];
     unsigned char* pinned[kRing] = {nullptr, nullptr, nullptr, nullptr};
     size_t pinned_cap[kRing] = {0, 0, 0, 0};
     hipEvent_t ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
     bool ev_pending[kRing] = {false, false, false, false};
     int ring = 0;
-    int nblk = 0;
     float* dev_state = nullptr;  // {step, lr, grad_scale, ticket, weight_decay, bc_step, bc1, bc2, beta1, beta2} for device-driven
                                  // stepping (graph replay); bc*: the bias corrections of step bc_step, left by the previous step
     bool hyper_set = false;
     const float* grad_div = nullptr;  // device float: divide gradients by it (all-reduced target count), or null
+    // The gradient norm's in-launch finish (grad_norm.hip), per handle and grow-only: [arrival ticket, padded to 16 B][one float per
+    // block].  The ticket is zeroed when the buffer is allocated -- never inside a capture -- and every launch leaves it zeroed.
+    unsigned char* norm_buf = nullptr;
+    int64_t norm_cap = 0;             // blocks
 
     ~FusedOptimizer() {
         (void)hipDeviceSynchronize();
-        if (dev) (void)hipFree(dev);
+        for (int i = 0; i < kSlots; ++i)
+            if (plan[i].dev) (void)hipFree(plan[i].dev);
+        if (norm_buf) (void)hipFree(norm_buf);
         if (dev_state) (void)hipFree(dev_state);
         for (int i = 0; i < kRing; ++i) {
             if (pinned[i]) (void)hipHostFree(pinned[i]);
@@ -212,8 +222,9 @@ namespace nnhip {
 // [blk_chunk int32 nblk], built on the host, compared bytewise with the last upload and re-sent only when something changed.
 // Adam / AdamW pass {p, g, m, v}; the rules of optim_rules.hip pass {p, g} and as many state tables as the rule has streams.
 int fused_optimizer_plan(void* opt, const char* who, int n, int n_tables, const void* const* const* tables, const int64_t* sizes,
-                         hipStream_t st, const unsigned char** dev_blob, int* nblk_out, int* chunk_out) {
+                         hipStream_t st, const unsigned char** dev_blob, int* nblk_out, int* chunk_out, int slot) {
     FusedOptimizer* fo = static_cast<FusedOptimizer*>(opt);
+    FusedOptimizer::Plan& pl = fo->plan[slot];
     *dev_blob = nullptr; *nblk_out = 0; *chunk_out = 0;
 
     // ---- build the plan blob ------------------------------------------------------------------
@@ -244,13 +255,13 @@ int fused_optimizer_plan(void* opt, const char* who, int n, int n_tables, const 
     }
 
     // ---- upload only if it changed ------------------------------------------------------------
-    if (blob != fo->last) {
-        if (bytes > fo->dev_cap) {
-            if (fo->dev) { (void)hipDeviceSynchronize(); (void)hipFree(fo->dev); fo->dev = nullptr; }
+    if (blob != pl.last) {
+        if (bytes > pl.dev_cap) {
+            if (pl.dev) { (void)hipDeviceSynchronize(); (void)hipFree(pl.dev); pl.dev = nullptr; }
             const size_t cap = bytes * 2;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&fo->dev), cap);
-            if (e != hipSuccess) { fo->dev_cap = 0; return hip_status(e, "hipMalloc(optimizer plan)"); }
-            fo->dev_cap = cap;
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&pl.dev), cap);
+            if (e != hipSuccess) { pl.dev_cap = 0; return hip_status(e, "hipMalloc(optimizer plan)"); }
+            pl.dev_cap = cap;
         }
         const int r = fo->ring;
         fo->ring = (fo->ring + 1) % FusedOptimizer::kRing;
@@ -266,16 +277,37 @@ int fused_optimizer_plan(void* opt, const char* who, int n, int n_tables, const 
             if (e != hipSuccess) return hip_status(e, "hipEventCreate(optimizer plan)");
         }
         memcpy(fo->pinned[r], blob.data(), bytes);
-        hipError_t e = hipMemcpyAsync(fo->dev, fo->pinned[r], bytes, hipMemcpyHostToDevice, st);
+        hipError_t e = hipMemcpyAsync(pl.dev, fo->pinned[r], bytes, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return hip_status(e, "hipMemcpyAsync(optimizer plan)");
         e = hipEventRecord(fo->ev[r], st);
         if (e != hipSuccess) return hip_status(e, "hipEventRecord(optimizer plan)");
         fo->ev_pending[r] = true;
-        fo->last.swap(blob);
-        fo->nblk = (int)nblk;
+        pl.last.swap(blob);
     }
 
-    *dev_blob = fo->dev; *nblk_out = (int)nblk; *chunk_out = (int)chunk;
+    *dev_blob = pl.dev; *nblk_out = (int)nblk; *chunk_out = (int)chunk;
+    return 0;
+}
+
+// The gradient norm's scratch on the handle: *ticket (one zeroed word) and *partials (>= nblk floats).  Grows only outside a capture:
+// hipMalloc is illegal inside one, and the eager warm-up steps of a captured loop have sized it already.
+int fused_optimizer_norm_scratch(void* opt, const char* who, int nblk, hipStream_t st, unsigned** ticket, float** partials) {
+    FusedOptimizer* fo = static_cast<FusedOptimizer*>(opt);
+    constexpr size_t kHead = 16;
+    if (nblk > fo->norm_cap) {
+        NNHIP_CHECK_ARG(!stream_capturing(st), NNHIP_ENOMEM, "%s: the handle's partials buffer would have to grow inside a stream capture "
+                        "(run the step eagerly once before capturing it)", who);
+        if (fo->norm_buf) { (void)hipDeviceSynchronize(); (void)hipFree(fo->norm_buf); fo->norm_buf = nullptr; fo->norm_cap = 0; }
+        const int64_t cap = (int64_t)nblk * 2 > 256 ? (int64_t)nblk * 2 : 256;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&fo->norm_buf), kHead + sizeof(float) * (size_t)cap);
+        if (e != hipSuccess) { fo->norm_buf = nullptr; return hip_status(e, "hipMalloc(gradient norm partials)"); }
+        e = hipMemset(fo->norm_buf, 0, kHead);
+        if (e == hipSuccess) e = hipDeviceSynchronize();     // the zeroed ticket is there before any stream's first launch reads it
+        if (e != hipSuccess) { (void)hipFree(fo->norm_buf); fo->norm_buf = nullptr; return hip_status(e, "hipMemset(gradient norm ticket)"); }
+        fo->norm_cap = cap;
+    }
+    *ticket = reinterpret_cast<unsigned*>(fo->norm_buf);
+    *partials = reinterpret_cast<float*>(fo->norm_buf + kHead);
     return 0;
 }
 }  // namespace nnhip

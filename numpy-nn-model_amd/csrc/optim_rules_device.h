@@ -69,9 +69,13 @@ __device__ __forceinline__ void rule1(float& p, float g, float& m, float& v, con
 
 // The optimizer handle's plan (optim.hip): one blob of `n_tables` pointer tables (n device pointers each, in the order given),
 // the sizes and the block -> (tensor, chunk) map, compared with the last upload and sent only when it changed.  Checks the sizes
-// and the pointers of non-empty tensors (`who` names the entry in the message).  *nblk == 0: nothing to launch.
+// and the pointers of non-empty tensors (`who` names the entry in the message).  *nblk == 0: nothing to launch.  `slot`: which of the
+// handle's plan caches (0 = the update's, 1 = the gradient norm's, grad_norm.hip).
 int fused_optimizer_plan(void* opt, const char* who, int n, int n_tables, const void* const* const* tables, const int64_t* sizes,
-                         hipStream_t st, const unsigned char** dev_blob, int* nblk, int* chunk);
+                         hipStream_t st, const unsigned char** dev_blob, int* nblk, int* chunk, int slot = 0);
 int fused_optimizer_state(void* opt, int step, float** dev_state, const float** grad_div);
+// The handle's scratch for the gradient norm's in-launch finish: one zeroed ticket word and >= nblk floats (grow-only; growing inside
+// a stream capture is NNHIP_ENOMEM).
+int fused_optimizer_norm_scratch(void* opt, const char* who, int nblk, hipStream_t st, unsigned** ticket, float** partials);
 
 }  // namespace nnhip

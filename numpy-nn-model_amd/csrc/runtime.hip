@@ -190,7 +190,7 @@ unsigned* sync_words() {
 
 }  // namespace nnhip
 
-extern "C" int nnhipVersion(void) { return 225; }
+extern "C" int nnhipVersion(void) { return 226; }
 
 extern "C" int nnhipDeviceError(void) { return nnhip::device_error_status("nnhipDeviceError"); }
 

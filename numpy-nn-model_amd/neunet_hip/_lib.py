@@ -181,6 +181,9 @@ _SIGNATURES = {
     "nnhipOptimizerRuleMultiTensorStep": (ctypes.c_int, [c_void_p, c_int32, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                          POINTER(c_void_p), POINTER(c_int64), c_double, c_double, c_double, c_double,
                                                          c_int32, c_float, c_void_p]),
+    "nnhipGradNormMultiTensor": (ctypes.c_int, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int64), c_int32, c_double, P, c_int32,
+                                                c_float, P, c_void_p]),
+    "nnhipScaleMultiTensor": (ctypes.c_int, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int64), P, c_void_p]),
     "nnhipConv2dForward": (ctypes.c_int, [P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConv2dBackward": (ctypes.c_int, [P, P, P, P, P, P, POINTER(Conv2dDesc), c_void_p]),
     "nnhipConvTranspose2dForward": (ctypes.c_int, [P, P, P, P, POINTER(ConvTranspose2dDesc), c_void_p]),

@@ -3,6 +3,7 @@ dense hot path (Linear, Conv2d, ReLU, Swish, Softmax, RMSNorm, CrossEntropyLoss)
 from .modules import Module, ModuleList, Sequential  # noqa: F401
 from .parameter import Parameter  # noqa: F401
 from . import experimental  # noqa: F401
+from . import utils  # noqa: F401  (clip_grad_norm_, get_grad_norm)
 from .experimental import (HIPConv2d as Conv2d, HIPCrossEntropyLoss, HIPLinear as Linear,  # noqa: F401
                            HIPLinearSwish as LinearSwish, HIPReLU as ReLU, HIPRMSNorm as RMSNorm,
                            HIPSoftmax as Softmax, HIPSwish as Swish, HIPFusedSwishAndMul as FusedSwishAndMul,

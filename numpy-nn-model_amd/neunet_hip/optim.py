@@ -55,7 +55,100 @@ class HIPFusedAdamW:
             p.grad = None
 
 
-class HIPFusedMultiTensorAdamW:
+NORM_L2, NORM_INF = 0, 1                  # include/neunet_hip.h: NNHIP_NORM_*
+
+
+def norm_type_id(norm_type):
+    """2 / inf -> NNHIP_NORM_L2 / NNHIP_NORM_INF; anything else is a ValueError (no other p-norm has a kernel)."""
+    try:
+        v = float(norm_type)
+    except (TypeError, ValueError):
+        raise ValueError(f"norm_type must be 2.0 or float('inf'), got {norm_type!r}") from None
+    if v == 2.0:
+        return NORM_L2
+    if v == float("inf"):
+        return NORM_INF
+    raise ValueError(f"norm_type must be 2.0 or float('inf'), got {norm_type!r}")
+
+
+def check_max_norm(max_norm):
+    """max_norm as a float; NaN, zero and negative values are a ValueError (the C entry answers NNHIP_EINVAL for them)."""
+    try:
+        v = float(max_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_norm must be a positive number, got {max_norm!r}") from None
+    if not v > 0.0:
+        raise ValueError(f"max_norm must be a positive number, got {max_norm!r}")
+    return v
+
+
+class _GradClipping:
+    """Gradient clipping by global norm inside step(), shared by every multi-tensor optimizer here (extension: the reference has
+    none).  `opt.max_grad_norm = 1.0` arms it: step() then launches nnhipGradNormMultiTensor on the tables it builds anyway --
+    ONE launch that leaves norm, divisor and a non-finite flag in four device floats -- and binds the handle's gradient divisor
+    to the divisor word, so the unchanged update launch applies torch's clip_coef without a pass over the gradients, a host read
+    or a memset: legal in a captured step.  The norm is that of the EFFECTIVE gradient (grad_scale and the user's grad_divisor
+    applied).  `opt.grad_norm_type` is 2.0 (default) or float('inf').  `opt.max_grad_norm = None` (default) disarms: step()
+    makes exactly the calls it made before.  Arm before a GraphedTrainStep is built; a new max_grad_norm between replays takes
+    effect at the next replay, as a new lr does.
+
+    `last_grad_norm` / `last_grad_nonfinite`: 1-element device views of the words; reading them is the caller's
+    synchronisation."""
+    _max_grad_norm = None
+    _grad_norm_type = 2.0
+    _clip_words = None            # torch.zeros(4): norm, divisor, non-finite flag, max_norm for device-driven stepping
+    _clip_divisor = None          # the view of word 1 the handle's divisor is bound to (one object: step() compares identities)
+    _dev_max_norm = None          # the max_norm last written to word 3
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        self._max_grad_norm = None if value is None else check_max_norm(value)
+
+    @property
+    def grad_norm_type(self):
+        return self._grad_norm_type
+
+    @grad_norm_type.setter
+    def grad_norm_type(self, value):
+        norm_type_id(value)
+        self._grad_norm_type = float(value)
+
+    @property
+    def last_grad_norm(self):
+        return None if self._clip_words is None else self._clip_words[0:1]
+
+    @property
+    def last_grad_nonfinite(self):
+        return None if self._clip_words is None else self._clip_words[2:3]
+
+    def _sync_clip_words(self):
+        """Word 3 follows max_grad_norm (a stream-ordered fill, only when it changed): what a captured norm launch reads."""
+        if self._max_grad_norm is None:
+            return
+        if self._clip_words is None:
+            import torch
+            self._clip_words = torch.zeros(4, dtype=torch.float32, device="cuda")
+            self._clip_divisor = self._clip_words[1:2]
+            self._dev_max_norm = None
+        if self._dev_max_norm != self._max_grad_norm:
+            self._clip_words[3:4].fill_(self._max_grad_norm)
+            self._dev_max_norm = self._max_grad_norm
+
+    def _clip_launch(self, n, stream):
+        """The norm launch over the first `n` entries of c_grads / c_sizes; returns the divisor word for the update to bind."""
+        self._sync_clip_words()
+        call_hip_function("nnhipGradNormMultiTensor", self.opt_ptr, n, ctypes.cast(self.c_grads, ctypes.POINTER(c_void_p)),
+                          ctypes.cast(self.c_sizes, ctypes.POINTER(c_int64)), norm_type_id(self._grad_norm_type),
+                          self._max_grad_norm, self.grad_divisor, 0 if self.device_step else self.t, self.grad_scale,
+                          self._clip_words, stream)
+        return self._clip_divisor
+
+
+class HIPFusedMultiTensorAdamW(_GradClipping):
     """One launch for all tensors (fused_adamw_multitensor.py:88-144).  Pointer tables are ctypes arrays in
     host memory whose entries are device pointers -- same contract as the reference."""
     decay_mode = DECOUPLED
@@ -105,9 +198,10 @@ class HIPFusedMultiTensorAdamW:
                 del p._fused_opt
 
     def can_fuse_into_backward(self):
-        """Nothing stands between this optimizer's gradients and its update: no gradient divisor (clipping), no live
-        collectives (data parallel: the gradients have to meet the other ranks' first)."""
-        if self.grad_divisor is not None:
+        """Nothing stands between this optimizer's gradients and its update: no gradient divisor (clipping), no armed
+        max_grad_norm (the norm needs every gradient before any update), no live collectives (data parallel: the gradients
+        have to meet the other ranks' first)."""
+        if self.grad_divisor is not None or self._max_grad_norm is not None:
             return False
         from .distributed import collectives_live
         return not collectives_live()
@@ -204,6 +298,10 @@ class HIPFusedMultiTensorAdamW:
         if idx == 0:
             return
         div = self.grad_divisor
+        if self._max_grad_norm is not None:    # armed: the norm launch first; the update divides by the word it leaves
+            if self.device_step:
+                self.sync_device_hyper()
+            div = self._clip_launch(idx, get_current_stream_ptr())
         if div is not self._bound_divisor:
             call_hip_function("nnhipFusedOptimizerSetGradDivisor", self.opt_ptr, div)
             self._bound_divisor = div
@@ -237,6 +335,8 @@ class HIPFusedMultiTensorAdamW:
         if self.device_step and cur != self._dev_hyper:
             call_hip_function("nnhipFusedOptimizerSetHyper", self.opt_ptr, cur[0], cur[1], cur[2], get_current_stream_ptr())
             self._dev_hyper = cur
+        if self.device_step:
+            self._sync_clip_words()           # a changed max_grad_norm -> word 3, which a captured norm launch reads
 
     def zero_grad(self):
         for p in self.params:
@@ -260,9 +360,10 @@ class Adam(HIPFusedMultiTensorAdamW):
 RULE_SGD, RULE_MOMENTUM, RULE_RMSPROP, RULE_ADAGRAD, RULE_ADADELTA, RULE_ADAMAX, RULE_NADAM = range(7)
 
 
-class _RuleOptimizer:
+class _RuleOptimizer(_GradClipping):
     """What the seven optimizers below share: one launch for all tensors (nnhipOptimizerRuleMultiTensorStep) on a handle of
     nnhipCreateFusedOptimizer, with everything of HIPFusedMultiTensorAdamW that is not Adam's -- `grad_scale`, `grad_divisor`,
+    `max_grad_norm` / `grad_norm_type` (_GradClipping),
     `use_device_step` / `sync_device_hyper` (hipGraph replay: GraphedTrainStep takes these classes as it takes Adam),
     parameters without a gradient skipped, strided gradients copied.  A subclass names its rule, its state streams (`m`, `v`:
     the reference's attribute names) and its two coefficients.
@@ -346,6 +447,10 @@ class _RuleOptimizer:
         if idx == 0:
             return
         div = self.grad_divisor
+        if self._max_grad_norm is not None:    # armed: the norm launch first; the update divides by the word it leaves
+            if self.device_step:
+                self.sync_device_hyper()
+            div = self._clip_launch(idx, get_current_stream_ptr())
         if div is not self._bound_divisor:
             call_hip_function("nnhipFusedOptimizerSetGradDivisor", self.opt_ptr, div)
             self._bound_divisor = div
@@ -379,6 +484,8 @@ class _RuleOptimizer:
         if self.device_step and cur != self._dev_hyper:
             call_hip_function("nnhipFusedOptimizerSetHyper", self.opt_ptr, cur[0], 0.0, cur[1], get_current_stream_ptr())
             self._dev_hyper = cur
+        if self.device_step:
+            self._sync_clip_words()           # a changed max_grad_norm -> word 3, which a captured norm launch reads
 
     def zero_grad(self):
         for p in self.params:

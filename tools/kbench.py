@@ -780,6 +780,77 @@ def main():
                   nbytes={"fold": 2 * nc, "pair": 5 * nc, "crossentropy": 2 * nc})
         del X, Y, dX, dlogp
 
+    if "gradnorm" in only:        # the one-launch global gradient norm (csrc/grad_norm.hip) on three parameter lists, beside a read-only
+        #                            stream of the same bytes and torch's clip_grad_norm_; then the C4 step in graph mode, armed / unarmed
+        sys.path.insert(0, os.path.join(ROOT, "examples"))
+        import gpt_tiny
+        import neunet_hip
+        import neunet_hip.nn as nn
+        from neunet_hip.distributed import GradBucket
+        from neunet_hip.graph import GraphedTrainStep
+        from neunet_hip.optim import Adam
+        cast = lambda a, t: ctypes.cast(a, ctypes.POINTER(t))  # noqa: E731
+        np.random.seed(1004)
+        c4 = dict(vocab=15000, d_model=512, n_heads=8, d_ff=2048, n_layers=6, seq=256)      # bench.py: C4
+
+        def c4_model():
+            model = gpt_tiny.build_gpt(c4["vocab"], c4["d_model"], c4["n_heads"], c4["d_ff"], c4["n_layers"], pad_idx=0, max_len=1024, fused=True)
+            ids_h = np.random.default_rng(4000).integers(3, c4["vocab"], (64, c4["seq"] + 1)).astype(np.int32)
+            ids = neunet_hip.Tensor(np.ascontiguousarray(ids_h[:, :-1]), dtype=np.int32, requires_grad=False, device="cuda")
+            tgt = neunet_hip.Tensor(np.ascontiguousarray(ids_h[:, 1:]).reshape(-1), dtype=np.int32, requires_grad=False, device="cuda")
+            loss_fn = nn.CrossEntropyLoss(ignore_index=0)
+
+            def fwd_bwd():
+                out, _ = model.forward(ids)
+                loss = loss_fn(out.reshape(out.shape[0] * out.shape[1], out.shape[2]), tgt)
+                loss.backward()
+                return loss
+
+            return model, fwd_bwd
+
+        model, fwd_bwd = c4_model()
+        fwd_bwd()                                                    # which parameters receive gradients (cross_attn never does)
+        c4_shapes = [tuple(p.data.shape) for p in model.parameters() if p.grad is not None]
+        del model, fwd_bwd
+        lists = {"C4 parameter list": c4_shapes, "one tensor 2^26": [(1 << 26,)], "README MLP": [(128, 784), (128,), (10, 128), (10,)]}
+        opt = _lib.load_hip_function("nnhipCreateFusedOptimizer")()
+        for tag, shapes in lists.items():
+            gs = [randn(*s) for s in shapes]
+            nt, numel = len(gs), sum(t.numel() for t in gs)
+            flat = torch.cat([t.reshape(-1) for t in gs])            # the same bytes as one buffer: the read-only stream
+            ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in gs])
+            sizes = (ctypes.c_int64 * nt)(*[t.numel() for t in gs])
+            words = torch.zeros(4, device=dev)
+            holders = [torch.nn.Parameter(torch.zeros(1, device=dev)) for _ in gs]
+            for h, t in zip(holders, gs):
+                h.data, h.grad = t, t.clone()
+            name = f"{tag} ({nt} tensors, {numel} el)"
+            for norm_id, ntag in ((0, "L2"), (1, "inf")):
+                report(f"gradnorm {ntag} {name}", *bench(lambda: call("nnhipGradNormMultiTensor", opt, nt, cast(ptrs, ctypes.c_void_p),
+                                                                        cast(sizes, ctypes.c_int64), norm_id, 1.0, None, 1, 1.0, words, st), args.iters), nbytes=4.0 * numel)
+            report(f"read-only stream (torch.sum) {name}", *bench(lambda: torch.sum(flat), args.iters), nbytes=4.0 * numel)
+            report(f"torch clip_grad_norm_ {name}", *bench(lambda: torch.nn.utils.clip_grad_norm_(holders, 1e30), args.iters), nbytes=4.0 * numel)
+            report(f"scale in place {name}", *bench(lambda: call("nnhipScaleMultiTensor", opt, nt, cast(ptrs, ctypes.c_void_p), cast(sizes, ctypes.c_int64),
+                                                                 words[1:2], st), args.iters), nbytes=8.0 * numel)
+            del gs, flat, holders
+        _lib.load_hip_function("nnhipDestroyFusedOptimizer")(opt)
+        for armed in (False, True, False, True):                     # alternated: the second pair shows the run-to-run spread
+            np.random.seed(1004)
+            model, fwd_bwd = c4_model()
+            adam = Adam(model.parameters(), lr=1.5e-4, betas=(0.9, 0.98), eps=1e-9)
+            adam.max_grad_norm = 1.0 if armed else None
+            fwd_bwd()
+            active = [p for p in model.parameters() if p.grad is not None]
+            adam.zero_grad()
+            gstep = GraphedTrainStep(fwd_bwd, adam, GradBucket(active, extra_scalars=1), warmup=2, count_nodes=True)
+            report(f"C4 step, graph, {'armed (max_grad_norm 1.0)' if armed else 'unarmed'}: {gstep.kernel_nodes} kernels",
+                   *bench(lambda: gstep(), args.iters))
+            if armed:
+                print(f"    grad norm {adam.last_grad_norm.item():.4f}  divisor {adam._clip_words[1].item():.4f}", flush=True)
+            gstep.release()
+            del gstep, adam, model, fwd_bwd, active
+            torch.cuda.empty_cache()
+
     if want("conv"):
         for (B, Cin, H, Cout) in [(256, 1, 28, 8), (256, 8, 14, 16)]:
             X = rnd(B, Cin, H, H)
